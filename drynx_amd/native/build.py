@@ -131,8 +131,8 @@ def build_sanitized(verbose: bool = True) -> str:
     workers = min(len(srcs), int(os.environ.get("MAX_JOBS", os.cpu_count() or 4)), 16)
     with cf.ThreadPoolExecutor(max_workers=workers) as ex:
         objs = list(ex.map(lambda s: _compile(s, hdr_digest, True), srcs))
-    cmd = [HIPCC, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-shared-libasan", "-fsanitize=address,undefined",
-           "-o", SAN_LIB, *objs, "-lpthread"]
+    cmd = [HIPCC, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-shared-libasan",
+           "-fsanitize=address,undefined", "-fno-gpu-sanitize", "-o", SAN_LIB, *objs, "-lpthread"]
     subprocess.run(cmd, check=True, timeout=600)
     if verbose:
         print(f"[drynx_amd] built {SAN_LIB}")

@@ -3,46 +3,43 @@
 paper's weights).  The reference only *logs* the comparison (it asserts
 nothing, :38-80); here we assert that our weights reach an approximated cost no
 worse than the paper's weights and generalise on the held-out split.
-Skipped when the read-only reference tree (CSV data) is not mounted."""
+The datasets (tests/golden/datasets) and the weight vectors of that test file
+(tests/golden/lr_paper_weights.json) are stored with the suite."""
+import json
 import os
-import re
 
 import pytest
 import torch
 
 from drynx_amd.models import logistic_regression as lr
 
-REF = "/root/reference"
-pytestmark = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "data")), reason="reference datasets absent")
-
-
-def _arr(src, name):
-    m = re.search(re.escape(name) + r"\s*=\s*\[\]float64\{(.*?)\}", src, re.S)
-    return [float(x) for x in m.group(1).replace("\n", "").split(",") if x.strip()]
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+DATA = os.path.join(GOLDEN, "datasets")
+with open(os.path.join(GOLDEN, "lr_paper_weights.json")) as _f:
+    WEIGHTS = json.load(_f)
 
 
 def test_spectf_weights_with_encryption_precision():
-    src = open(os.path.join(REF, "lib/encoding/logistic_regression_dataset_test.go")).read()
-    init = _arr(src, "initialWeights :")
-    paper = _arr(src, "var SPECTFpaperWeightsWithEncryption")
-    X, y = lr.load_csv_dataset(os.path.join(REF, "data/SPECTF_heart_dataset_training.txt"))
+    init = WEIGHTS["SPECTF"]["initial_weights"]
+    paper = WEIGHTS["SPECTF"]["paper_weights"]["encrypted"]
+    X, y = lr.load_csv_dataset(os.path.join(DATA, "SPECTF_heart_dataset_training.txt"))
     Xa = lr.augment(lr.standardise(X))
     ap = [lr.round_precision(a, 1e2).to(torch.float64) / 1e2 for a in lr.approx_coefficients(Xa, y, 2)]
     w = lr.find_minimum_weights(ap, init, X.shape[0], 1.0, 0.012, 450)
     assert lr.cost(torch.tensor(w), ap, X.shape[0], 1.0) <= lr.cost(torch.tensor(paper), ap, X.shape[0], 1.0)
-    Xt, yt = lr.load_csv_dataset(os.path.join(REF, "data/SPECTF_heart_dataset_testing.txt"))
+    Xt, yt = lr.load_csv_dataset(os.path.join(DATA, "SPECTF_heart_dataset_testing.txt"))
     m, s = lr.compute_means_sds(X)
     met = lr.metrics(lr.predict(Xt, w, m, s), yt)
     assert met["accuracy"] > 0.6 and met["auc"] > 0.7
 
 
 def test_pima_training_converges():
-    X, y = lr.load_csv_dataset(os.path.join(REF, "data/Pima_dataset_training.txt"))
+    X, y = lr.load_csv_dataset(os.path.join(DATA, "Pima_dataset_training.txt"))
     Xa = lr.augment(lr.standardise(X))
     ap = [lr.round_precision(a, 1e2).to(torch.float64) / 1e2 for a in lr.approx_coefficients(Xa, y, 2)]
     w = lr.find_minimum_weights(ap, [0.0] * (X.shape[1] + 1), X.shape[0], 1.0, 0.1, 200)
     m, s = lr.compute_means_sds(X)
-    Xt, yt = lr.load_csv_dataset(os.path.join(REF, "data/Pima_dataset_testing.txt"))
+    Xt, yt = lr.load_csv_dataset(os.path.join(DATA, "Pima_dataset_testing.txt"))
     assert lr.metrics(lr.predict(Xt, w, m, s), yt)["accuracy"] > 0.7
 
 
@@ -59,29 +56,16 @@ def test_pima_training_converges():
 # the pregnancy count, so its own Pima comparison ran on mislabeled data: the
 # label is read from column 8 here.
 _FIXTURES = {
-    "SPECTF": ("data/SPECTF_heart_dataset_training.txt", 0, "initialWeights :", 0.012, 450,
-               {False: "var SPECTFpaperWeightsWithoutEncryption", True: "var SPECTFpaperWeightsWithEncryption"}),
-    "Pima": ("data/Pima_dataset.txt", 8, "initialWeights := []float64{", 0.1, 200,
-             {False: "var PimaPaperWeightsWithoutEncryption", True: "var PimaPaperWeightsWithEncryption"}),
+    "SPECTF": ("SPECTF_heart_dataset_training.txt", 0, 0.012, 450),
+    "Pima": ("Pima_dataset.txt", 8, 0.1, 200),
 }
 
 
-def _arr_after(src, marker):
-    i = src.index(marker)
-    body = src[src.index("{", i) + 1: src.index("}", i)]
-    body = "\n".join(ln.split("//")[0] for ln in body.splitlines())
-    return [float(x) for x in body.replace("\n", "").split(",") if x.strip()]
-
-
 def _fixture(dataset, encrypted):
-    src = open(os.path.join(REF, "lib/encoding/logistic_regression_dataset_test.go")).read()
-    path, label, init_marker, step, iters, paper_var = _FIXTURES[dataset]
-    if dataset == "Pima":
-        init = _arr_after(src[src.index("func getParametersForPima"):], init_marker)
-    else:
-        init = _arr(src, init_marker)
-    paper = _arr_after(src, paper_var[encrypted])
-    X, y = lr.load_csv_dataset(os.path.join(REF, path), label_col=label)
+    path, label, step, iters = _FIXTURES[dataset]
+    init = WEIGHTS[dataset]["initial_weights"]
+    paper = WEIGHTS[dataset]["paper_weights"]["encrypted" if encrypted else "clear"]
+    X, y = lr.load_csv_dataset(os.path.join(DATA, path), label_col=label)
     assert len(init) == len(paper) == X.shape[1] + 1
     Xa = lr.augment(lr.standardise(X))
     if encrypted:  # per record, rounded to 1e2, then summed (the DPs' integer encoding)

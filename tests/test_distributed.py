@@ -94,7 +94,8 @@ def _bench_line(r):
     return json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
 
 
-_SMALL = ["--steps", "1", "--warmup", "0", "--records", "2000", "--features", "2", "--max-iter", "5", "--device", "cpu"]
+_SMALL = ["--steps", "1", "--warmup", "0", "--records", "2000", "--features", "2", "--max-iter", "5", "--device", "cpu",
+          "--full"]
 
 
 @pytest.mark.slow
@@ -156,6 +157,28 @@ def test_bench_self_launches_two_ranks():
     assert d["n_gpus"] == 2 and d["all_proofs_valid"] and d["result_ok"] and len(d["ranks"]) == 2
 
 
+@pytest.mark.slow
+def test_bench_plain_run_full_and_dump(tmp_path):
+    """A plain run leaves the clear-text recomputation out (result_ok null),
+    ``--full`` runs it; ``--dump-outputs`` writes the last timed query's
+    outputs as float64 arrays, identical from run to run (seeded records)."""
+    import numpy as np
+
+    plain = [a for a in _SMALL if a != "--full"]
+    d1 = _run_bench(1, plain + ["--dump-outputs", str(tmp_path / "a")])
+    d2 = _run_bench(1, plain + ["--full", "--dump-outputs", str(tmp_path / "b")])
+    assert d1["all_proofs_valid"] and d1["result_ok"] is None and d1["steps"] == 1 and d1["ms_per_step"] > 0
+    assert d2["all_proofs_valid"] and d2["result_ok"] is True
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["aggregate.npy", "proof_codes.npy", "result.npy"] == sorted(os.listdir(tmp_path / "b"))
+    a, b = ({n: np.load(tmp_path / s / n) for n in names} for s in ("a", "b"))
+    for n in names:
+        assert a[n].dtype == np.float64 and np.array_equal(a[n], b[n]), n
+    n_out = d1["config"]["range_proof"]["proofs_per_query"] // d1["config"]["dps"]
+    assert a["aggregate.npy"].shape == (n_out,) and a["result.npy"].shape == (3,)  # d = 2: 3 weights
+    assert a["proof_codes.npy"].size > 0 and (a["proof_codes.npy"] == 1).all()
+
+
 def test_bench_rejects_world_mismatch():
     """Under a launcher whose world differs from --gpus the bench refuses to
     print a number labelled with the wrong GPU count."""
@@ -201,7 +224,7 @@ def test_two_ranks_sharded_tables_and_node_ledger():
     content-addressed ledger payloads (each written once on the node, the
     other rank referencing it) and every VN's stored proofs read back."""
     small = ["--steps", "1", "--warmup", "1", "--records", "2000", "--features", "2", "--max-iter", "5",
-             "--device", "cpu", "--deterministic-sigs", "--table-digest"]
+             "--device", "cpu", "--deterministic-sigs", "--table-digest", "--full"]
     env = {"DRYNX_PROVER_TABLE_BITS": "7"}
     d2 = _run_bench(2, small + ["--verification-sharding", "2", "--check-ledger"], env)
     d1 = _run_bench(1, small, env)

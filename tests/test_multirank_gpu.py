@@ -15,7 +15,7 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SMALL = ["--steps", "2", "--warmup", "1", "--records", "20000", "--features", "6", "--max-iter", "20",
-         "--device", "cuda:0", "--deterministic-sigs", "--table-digest"]
+         "--device", "cuda:0", "--deterministic-sigs", "--table-digest", "--full"]
 
 
 def _bench(gpus: int, extra: list, timeout: int = 300) -> dict:

@@ -28,7 +28,8 @@ def test_rccl_dist_comm_one_rank():
 
 
 def test_bench_on_rccl_comm_one_rank():
-    r = _torchrun(["bench.py", "--steps", "1", "--warmup", "1", "--features", "6", "--records", "20000"], 29643)
+    r = _torchrun(["bench.py", "--steps", "1", "--warmup", "1", "--features", "6", "--records", "20000",
+                   "--full"], 29643)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     line = json.loads([x for x in r.stdout.splitlines() if x.startswith("{")][-1])
     assert line["all_proofs_valid"] and line["result_ok"] and line["n_gpus"] == 1

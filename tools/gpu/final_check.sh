@@ -8,16 +8,16 @@ export HSA_ENABLE_IPC_MODE_LEGACY=0 TMPDIR=/tmp
 step() { local name=$1; shift; timeout -k 10 "$@" > $O/$name.log 2>&1; local rc=$?; tail -1 $O/$name.log | cut -c1-300; if [ $rc -ne 0 ]; then tail -40 $O/$name.log; exit $rc; fi; }
 step pytest 900 python -u -m pytest ${FINAL_TESTS:-tests} -m gpu -v --timeout 400 --timeout-method thread
 if [ "${FINAL_STEPS:-all}" = quick ]; then
-  step bench 300 python -u bench.py --steps 20 --warmup 5 --json-out $O/bench.json
+  step bench 300 python -u bench.py --steps 20 --warmup 5 --full --json-out $O/bench.json
   step share 500 python -u tools/rank_share.py --world 8 --reps 3 --ctrl-json profiles/r5/final/ctrl_w8.json --json-out $O/rank_share_w8.json
   step sharel 500 python -u tools/rank_share.py --world 8 --reps 3 --vn-mode local --ctrl-json profiles/r5/final/ctrl_w8.json --json-out $O/rank_share_w8_local.json
   exit 0
 fi
 step smoke 300 python -u -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')"
-step bench 300 python -u bench.py --steps 20 --warmup 5 --json-out $O/bench.json
-step bench100 600 python -u bench.py --steps 100 --warmup 5 --check-ledger --json-out $O/bench100.json
-step fault 300 python -u bench.py --steps 10 --warmup 3 --fault-dp 3 --json-out $O/fault.json
-step u0l0 300 python -u bench.py --steps 20 --warmup 5 --u 0 --l 0 --json-out $O/u0l0.json
+step bench 300 python -u bench.py --steps 20 --warmup 5 --full --json-out $O/bench.json
+step bench100 600 python -u bench.py --steps 100 --warmup 5 --full --check-ledger --json-out $O/bench100.json
+step fault 300 python -u bench.py --steps 10 --warmup 3 --full --fault-dp 3 --json-out $O/fault.json
+step u0l0 300 python -u bench.py --steps 20 --warmup 5 --full --u 0 --l 0 --json-out $O/u0l0.json
 OMP_NUM_THREADS=1 step ctrl 300 python -u tools/ctrl_round.py --world 8 --rounds 300 --json-out $O/ctrl_w8.json
 step share 500 python -u tools/rank_share.py --world 8 --reps 3 --serial-json $O/u0l0.json --ctrl-json $O/ctrl_w8.json --json-out $O/rank_share_w8.json
 step sharel 500 python -u tools/rank_share.py --world 8 --reps 3 --vn-mode local --serial-json $O/u0l0.json --ctrl-json $O/ctrl_w8.json --json-out $O/rank_share_w8_local.json
