@@ -16,7 +16,7 @@
 #define DX_HD __host__ __device__ __forceinline__
 // DX_NI: out-of-line tower/curve functions (small code, shared by the kernels
 // of a translation unit).  A TU may predefine it as force-inline to get one
-// register-allocated body per kernel instead (dx_fold_inl.hip).
+// register-allocated body per kernel instead (dx_fold.hip, dx_check_inl.hip).
 #ifndef DX_NI
 #define DX_NI __host__ __device__ __noinline__ inline
 #endif

@@ -51,6 +51,15 @@ DX_NI void miller_add(Fp2 &X, Fp2 &Y, Fp2 &Z, const Fp2 &x2, const Fp2 &y2, cons
   X = X3; Y = Y3; Z = Z3;
 }
 
+// Lines of one Miller loop below: a doubling per digit of ATE_NAF under the
+// top one, an addition per nonzero digit among them, and the 2 Frobenius lines.
+constexpr int count_add_steps() {
+  int c = 0;
+  for (int i = ATE_NAF_LEN - 2; i >= 0; i--) c += ATE_NAF[i] != 0 ? 1 : 0;
+  return c;
+}
+constexpr int kMillerSteps = (ATE_NAF_LEN - 1) + count_add_steps() + 2;
+
 // Miller loop f_{6u+2,Q}(P) * l_{T,pi(Q)} * l_{T',-pi^2(Q)} (not final-exponentiated).
 DX_NI Fp12 miller_loop(const G1A &P, const G2A &Q) {
   if (P.is_inf() || Q.is_inf()) return Fp12::one();

@@ -1,4 +1,5 @@
-// Fused range-proof kernels (K15 prove, K16 batched verify).
+// Range-proof prover kernels (K15) and the GT segmented products of the
+// batched verifier's bucket multi-exponentiation (K16).
 //
 // Reference: lib/range/range_proof.go.  Per value, digit j and server i the
 // prover publishes a_ij = e(-s_j B, V_ij) * e(t_j B, B2) (:396-397) and the
@@ -7,10 +8,13 @@
 //
 // Here:
 //   prove  : a_ij = FE(ML(-s_j B, V_ij)) * gT^{t_j}   (gT = e(B,B2) comb table)
-//   verify : all (p,i,j) of a list are folded with random 64-bit weights rho:
+//   verify : all (p,i,j) of a VN inbox are folded with random 64-bit weights rho:
 //            FE(prod_pij ML(rho (Zphi_j B - c y_i), V_ij)) * prod_pij a_ij^rho
-//            == gT^{sum rho Zv}: ONE final exponentiation for the whole list.  One Miller loop per (p,i,j)
-//            instead of three pairings.
+//            == gT^{sum rho Zv}, ONE final exponentiation for the whole inbox.
+//            The Miller product is regrouped by bilinearity (dx_rpmsm.hip) and
+//            folded by dx_fold.hip / dx_ufold_coop.hip; this file has the
+//            prod a^rho side: the segmented products and bucket weights of
+//            its multi-exponentiation (native/__init__.py multi_exp_grouped).
 // Item index: it = (p * S + i) * L + j.
 #include "common.h"
 #include "../bn254/gt_coop.h"
@@ -68,71 +72,7 @@ int dx_rp_prove_a_tab(int on_gpu, void *stream, const uint32_t *gphi_tables, con
   return 0;
 }
 
-// f[it] = ML(rho (ZB[p*L+j] - Y[p*S+i]), V[it]),  g[it] = a[it]^rho
-// (the final exponentiation applies to the Miller product only: a_ij is already in GT)
-int dx_rp_verify_items(int on_gpu, void *stream, const uint32_t *ZB_jac, const uint32_t *Y_jac, const uint32_t *rho,
-                       const uint32_t *V_aff, const uint32_t *a, uint32_t *f_out, uint32_t *g_out, int64_t n_items,
-                       int S, int L) {
-  auto op = [=] __host__ __device__(int64_t it) {
-    int64_t j = it % L;
-    int64_t pi = it / L;  // p*S + i
-    int64_t p = pi / S;
-    G1J T = jadd(at<G1J>(ZB_jac, p * L + j), jneg(at<G1J>(Y_jac, pi)));
-    G1A P = to_affine(scalar_mul(T, rho + 8 * it));
-    at<Fp12>(f_out, it) = miller_loop(P, at<G2A>(V_aff, it));
-    at<Fp12>(g_out, it) = gt_pow(at<Fp12>(a, it), rho + 8 * it);
-  };
-  return run(on_gpu, stream, n_items, op, true, "rp_verify_items");
-}
-
 }  // extern "C"
-
-// GPU-only fused Miller fold: every 64-lane workgroup computes the Miller
-// values of 64 items and folds them with an LDS tree, writing one Fp12 per
-// workgroup -- the [n_items] intermediate never reaches HBM.  The a^rho side
-// of the batch equation is a separate bucket multi-exponentiation
-// (dx_gt_slice_prod below + rp_verify_products in native/__init__.py), so this
-// kernel carries only the Miller-loop state.
-namespace {
-constexpr int kVW = 64;
-__global__ void __launch_bounds__(kVW) DX_OCC rp_verify_fold_kernel(const uint32_t *ZB_jac, const uint32_t *Y_jac,
-                                                              const uint32_t *rho, const uint32_t *V_aff,
-                                                              uint32_t *f_blk, int64_t n_items, int S, int L) {
-  // 32 Fp12 of LDS (12 KiB): the upper half of the live lanes hands its value
-  // down each level.  With 24 KiB (one slot per lane) the LDS capped a CU at 6
-  // of these workgroups, so a 99392-item batch (1553 workgroups) left 17 for a
-  // second, nearly empty round; at 12 KiB the register file (2 waves per SIMD,
-  // 8 per CU) is the cap and the whole batch is resident at once.
-  __shared__ Fp12 sf[kVW / 2];
-  const int lane = threadIdx.x;
-  const int64_t it = (int64_t)blockIdx.x * kVW + lane;
-  Fp12 f = Fp12::one();
-  if (it < n_items) {
-    int64_t j = it % L;
-    int64_t pi = it / L;
-    int64_t p = pi / S;
-    G1J T = jadd(at<G1J>(ZB_jac, p * L + j), jneg(at<G1J>(Y_jac, pi)));
-    G1A P = to_affine(scalar_mul(T, rho + 8 * it));
-    f = miller_loop(P, at<G2A>(V_aff, it));
-  }
-  for (int s = kVW / 2; s > 0; s >>= 1) {
-    if (lane >= s && lane < 2 * s) sf[lane - s] = f;
-    __syncthreads();
-    if (lane < s) f = mul(f, sf[lane]);
-    __syncthreads();
-  }
-  if (lane == 0) at<Fp12>(f_blk, blockIdx.x) = f;
-}
-}  // namespace
-
-extern "C" int dx_rp_verify_fold(void *stream, const uint32_t *ZB_jac, const uint32_t *Y_jac, const uint32_t *rho,
-                                 const uint32_t *V_aff, uint32_t *f_blk, int64_t n_items, int S, int L) {
-  if (n_items <= 0) return 0;
-  int64_t blocks = (n_items + kVW - 1) / kVW;
-  hipLaunchKernelGGL(rp_verify_fold_kernel, dim3((unsigned)blocks), dim3(kVW), 0, (hipStream_t)stream, ZB_jac, Y_jac,
-                     rho, V_aff, f_blk, n_items, S, L);
-  return check_hip(hipGetLastError(), "rp_verify_fold");
-}
 
 // Segmented GT products (bucket accumulation of a multi-exponentiation):
 //   out[s] = prod_{k < len[s]} src[idx ? idx[start[s] + k] : start[s] + k]

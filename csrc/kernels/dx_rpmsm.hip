@@ -175,17 +175,6 @@ DX_HD void slice_sum_one(const uint32_t *src, const int32_t *idx, const int64_t 
   at<G2J>(out, s) = acc;
 }
 
-DX_HD void mul_small_one(const uint32_t *in_jac, const int32_t *d, uint32_t *out, int64_t i) {
-  const G2J p = at<G2J>(in_jac, i);
-  const uint32_t k = (uint32_t)d[i];
-  G2J r = G2J::inf();
-  for (int bit = 30; bit >= 0; bit--) {
-    r = jdbl(r);
-    if ((k >> bit) & 1u) r = jadd(r, p);
-  }
-  at<G2J>(out, i) = r;
-}
-
 DX_HD void horner_one(const uint32_t *S_jac, uint32_t *out_aff, int W, int c, int64_t stride, int64_t offset,
                       int64_t g) {
   G2J acc = at<G2J>(S_jac, g * W + W - 1);
@@ -345,11 +334,6 @@ __global__ void __launch_bounds__(kWG) DX_OCC slice_sum_kernel(const uint32_t *s
   DX_TID();
   if (i < n) slice_sum_one(src, idx, start, len, out, src_aff, idx_mod, i);
 }
-__global__ void __launch_bounds__(kWG) DX_OCC mul_small_kernel(const uint32_t *in, const int32_t *d, uint32_t *out,
-                                                              int64_t n) {
-  DX_TID();
-  if (i < n) mul_small_one(in, d, out, i);
-}
 __global__ void __launch_bounds__(kWG) DX_OCC chunk_weight_kernel(const uint32_t *B, const int32_t *d,
                                                                  const int64_t *start, const int32_t *len,
                                                                  const int32_t *base, uint32_t *out, int64_t n) {
@@ -445,17 +429,6 @@ int dx_g2_slice_sum(int on_gpu, void *stream, const uint32_t *src, const int32_t
   hipLaunchKernelGGL(slice_sum_kernel, grid_of(n_slices), dim3(kWG), 0, (hipStream_t)stream, src, idx, start, len,
                      out, src_aff, idx_mod, n_slices);
   return check_hip(hipGetLastError(), "g2_slice_sum");
-}
-
-// out[i] = d[i] * in[i] (Jacobian), 0 <= d[i] < 2^31: the Pippenger bucket weights
-int dx_g2_mul_small(int on_gpu, void *stream, const uint32_t *in_jac, const int32_t *d, uint32_t *out, int64_t n) {
-  if (n <= 0) return 0;
-  if (!on_gpu) {
-    host_for_each(n, [=](int64_t i) { mul_small_one(in_jac, d, out, i); });
-    return 0;
-  }
-  hipLaunchKernelGGL(mul_small_kernel, grid_of(n), dim3(kWG), 0, (hipStream_t)stream, in_jac, d, out, n);
-  return check_hip(hipGetLastError(), "g2_mul_small");
 }
 
 // out[ch] = sum_{i in chunk ch} d[i] * B[i] (Jacobian; chunk = start/len over

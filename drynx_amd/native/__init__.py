@@ -50,7 +50,6 @@ def _load():
 _P = ctypes.c_void_p
 _I = ctypes.c_int
 _L = ctypes.c_int64
-_U64 = ctypes.c_uint64
 
 _SIGS = {
     "dx_fp_to_mont": [_I, _P, _P, _P, _L],
@@ -108,7 +107,6 @@ _SIGS = {
     "dx_g2_x_compress": [_I, _P, _P, _P, _P, _P, _L],
     "dx_g2_x_decompress": [_I, _P, _P, _P, _P, _P, _L],
     "dx_gt_t2_decompress": [_I, _P, _P, _P, _L],
-    "dx_rp_verify_fold": [_P, _P, _P, _P, _P, _P, _L, _I, _I],
     "dx_gt_slice_prod": [_I, _P, _P, _P, _P, _P, _P, _L],
     "dx_gt_chunk_weight": [_I, _P, _P, _P, _P, _P, _P, _P, _L],
     "dx_g1_mul_glv": [_P, _P, _P, _P, _P, _L, _I],
@@ -131,22 +129,15 @@ _SIGS = {
     "dx_g2_subgroup": [_I, _P, _P, _P, _L],
     "dx_limbs_canonical": [_I, _P, _P, _I, _P, _L],
     "dx_g1j_on_curve": [_I, _P, _P, _P, _L],
-    "dx_rp_points_inl": [_P, _P, _P, _P, _P, _L, _I, _I],
-    "dx_fold_steps_inl": [],
-    "dx_rp_lines_inl": [_P, _P, _P, _P, _L, _L, _L],
-    "dx_rp_accum_inl": [_P, _P, _P, _L, _I],
-    "dx_rp_coeffs_inl": [_P, _P, _P, _L],
-    "dx_rp_accum_p_inl": [_P, _P, _P, _P, _P, _L, _L, _I, _I],
-    "dx_rp_verify_items": [_I, _P, _P, _P, _P, _P, _P, _P, _P, _L, _I, _I],
+    "dx_fold_steps": [],
+    "dx_rp_coeffs": [_P, _P, _P, _L],
     "dx_int_moments": [_I, _P, _P, _L, _I, _P, _L, _P, _I, _P, _P],
     "dx_sha256_rows": [_I, _P, _P, _L, _L, _L, _L, _P],
     "dx_sha256_segments": [_I, _P, _P, _L, _L, _L, _P],
-    "dx_rp_points_glv": [_P, _P, _P, _P, _P, _P, _L, _I, _I, _I],
     "dx_g1_aff_to_uv": [_I, _P, _P, _L],
-    "dx_rp_ncoeffs_inl": [_P, _P, _P, _P, _L],
-    "dx_rp_accum_n_inl": [_P, _P, _P, _P, _P, _L, _L, _I, _I],
+    "dx_rp_ncoeffs": [_P, _P, _P, _P, _L],
+    "dx_rp_accum_n": [_P, _P, _P, _P, _P, _L, _L, _I, _I],
     "dx_ufold_coop_raw": [_P, _P, _P, _P, _P, _L, _L, _L],
-    "dx_ufold_coop_steps": [],
     "dx_gt_frob8": [_I, _P, _P, _P, _L],
     "dx_gls6_entries": [],
     "dx_g2_gls6_table": [_I, _P, _P, _P, _P, _L],
@@ -157,7 +148,6 @@ _SIGS = {
     "dx_g2_joint_table": [_I, _P, _P, _P, _L],
     "dx_rp_u_joint": [_I, _P, _P, _P, _P, _L, _I, _I, _L, _P],
     "dx_g2_slice_sum": [_I, _P, _P, _P, _P, _P, _P, _L, _I, _L],
-    "dx_g2_mul_small": [_I, _P, _P, _P, _P, _L],
     "dx_g2_horner": [_I, _P, _P, _P, _I, _I, _I, _L, _L],
     "dx_rp_msm_uv": [_I, _P, _P, _P, _L, _I, _L],
     "dx_msm_keys": [_I, _P, _P, _P, _L, _L, _I, _I, _P, _P],
@@ -246,10 +236,6 @@ def _call(name, *args):
 def _rows(t: torch.Tensor, width: int) -> int:
     assert t.dtype == torch.int32 and t.shape[-1] == width, (t.dtype, t.shape, width)
     return t.numel() // width
-
-
-def empty_like_rows(ref: torch.Tensor, n: int, width: int) -> torch.Tensor:
-    return torch.empty((n, width), dtype=torch.int32, device=ref.device)
 
 
 # ----------------------------------------------------------------------------- field
@@ -1305,98 +1291,6 @@ def rp_challenges(C_aff: torch.Tensor, b_words: torch.Tensor, y_words: torch.Ten
     return out
 
 
-def rp_verify_items(ZB_jac, Y_jac, rho, V_aff, a, S: int, L: int):
-    n = _rows(V_aff, 32)
-    f = torch.empty((n, 96), dtype=torch.int32, device=V_aff.device)
-    gg = torch.empty((n, 96), dtype=torch.int32, device=V_aff.device)
-    g, s = _ctx(ZB_jac, Y_jac, rho, V_aff, a)
-    _call("dx_rp_verify_items", g, s, _ptr(ZB_jac), _ptr(Y_jac), _ptr(rho), _ptr(V_aff), _ptr(a), _ptr(f), _ptr(gg),
-          n, S, L)
-    return f, gg
-
-
-def rp_verify_products(ZB_jac, Y_jac, rho, V_aff, a, S: int, L: int):
-    """(prod_it ML_it, prod_it a_it^rho_it) as two [1, 96] HOST tensors.
-    GPU: the Miller values fold per 64-item workgroup in LDS (dx_rp_verify_fold)
-    and the a^rho product is a bucket multi-exponentiation (gt_multi_exp64);
-    host: per-item values + product tree."""
-    g, s = _ctx(ZB_jac, Y_jac, rho, V_aff, a)
-    if not g:
-        f, gg = rp_verify_items(ZB_jac, Y_jac, rho, V_aff, a, S, L)
-        return gt_prod(f.view(-1, 1, 96), chunk=4).view(1, 96), gt_prod(gg.view(-1, 1, 96), chunk=4).view(1, 96)
-    plan = _multi_exp64_plan(rho)  # index work first: its one host sync does not wait for the Miller fold
-    fb = rp_verify_fold(ZB_jac, Y_jac, rho, V_aff, S, L)
-    G = _multi_exp64_run(a, plan)
-    return _finish_prod_on_host(fb), G
-
-
-def rp_verify_fold(ZB_jac, Y_jac, rho, V_aff, S: int, L: int) -> torch.Tensor:
-    """Launch the fused Miller fold (GPU, asynchronous): [ceil(n/64), 96]
-    per-workgroup Miller products on the current stream."""
-    n = _rows(V_aff, 32)
-    _, s = _ctx(ZB_jac, Y_jac, rho, V_aff)
-    fb = torch.empty(((n + 63) // 64, 96), dtype=torch.int32, device=V_aff.device)
-    rc = _raw_call("dx_rp_verify_fold", s, _ptr(ZB_jac), _ptr(Y_jac), _ptr(rho), _ptr(V_aff), _ptr(fb), n, S, L)
-    if rc:
-        raise RuntimeError(f"dx_rp_verify_fold failed rc={rc}")
-    return fb
-
-
-# inl: tower force-inlined into the fold kernels (12.4M Miller loops/s on one
-# MI355X vs 10.0M for ni, the out-of-line tower; tools/fold_bench.py)
-FOLD_VARIANT = "inl"  # dx_fold_inl.hip (force-inlined tower functions; the out-of-line build lost its A/B)
-
-
-def rp_fold_points(ZB_jac: torch.Tensor, Y_jac: torch.Tensor, rho: torch.Tensor, S: int, L: int,
-                   variant: str | None = None, out: torch.Tensor | None = None) -> torch.Tensor:
-    """GPU: P_it = affine(rho_it (ZB[p*L+j] - Y[p*S+i])), it = (p*S+i)*L + j,
-    one fused launch -> [n, 16] (n = rows of rho), or into ``out``."""
-    v = variant or FOLD_VARIANT
-    n = _rows(rho, 8)
-    assert _rows(ZB_jac, 24) * S == n and _rows(Y_jac, 24) * L == n and ZB_jac.is_cuda
-    P = out if out is not None else torch.empty((n, 16), dtype=torch.int32, device=rho.device)
-    assert P.shape == (n, 16) and P.is_contiguous()
-    _, s = _ctx(ZB_jac, Y_jac, rho)
-    rc = _raw_call(f"dx_rp_points_{v}", s, _ptr(ZB_jac.contiguous()), _ptr(Y_jac.contiguous()), _ptr(rho),
-                                                  _ptr(P), n, S, L)
-    if rc:
-        raise RuntimeError(f"dx_rp_points_{v} failed rc={rc}")
-    return P
-
-
-def rp_fold_lines(P_aff: torch.Tensor, V_aff: torch.Tensor, variant: str | None = None,
-                  period: int | None = None) -> torch.Tensor:
-    """Phase 1 of the two-phase Miller fold (GPU): the sparse line values of
-    every item's Miller loop evaluated at its P -> flat int32 image
-    [steps * 12 * n * 4] (csrc/kernels/fold_body.h).  ``period``: item it
-    pairs P[it] with V[it % period] (several verifiers' batches, each padded
-    to ``period`` rows, in one launch)."""
-    v = variant or FOLD_VARIANT
-    n = _rows(P_aff, 16)
-    nv = _rows(V_aff, 32)
-    period = period or n
-    assert nv <= period and n % period == 0 and P_aff.is_cuda
-    steps = getattr(_load(), f"dx_fold_steps_{v}")()
-    lines = torch.empty((steps * 12 * n * 4,), dtype=torch.int32, device=P_aff.device)
-    _, s = _ctx(P_aff, V_aff)
-    rc = _raw_call(f"dx_rp_lines_{v}", s, _ptr(P_aff), _ptr(V_aff), _ptr(lines), n, period, nv)
-    if rc:
-        raise RuntimeError(f"dx_rp_lines_{v} failed rc={rc}")
-    return lines
-
-
-def rp_fold_accum(lines: torch.Tensor, n: int, K: int = 4, variant: str | None = None) -> torch.Tensor:
-    """Phase 2: per-workgroup products of the Miller values of 64*K items,
-    K items per lane sharing one accumulator -> [ceil(n / (64 K)), 96]."""
-    v = variant or FOLD_VARIANT
-    fb = torch.empty(((n + 64 * K - 1) // (64 * K), 96), dtype=torch.int32, device=lines.device)
-    _, s = _ctx(lines)
-    rc = _raw_call(f"dx_rp_accum_{v}", s, _ptr(lines), _ptr(fb), n, K)
-    if rc:
-        raise RuntimeError(f"dx_rp_accum_{v} failed rc={rc}")
-    return fb
-
-
 # GLV batch weights (csrc/kernels/dx_glv.hip): rho = a + b * GLV_LAMBDA mod r with
 # a, b 32-bit; phi(x, y) = (GLV_BETA x, y) = [GLV_LAMBDA] on G1; x^GLV_LAMBDA =
 # x^(p^8) on GT.  Both constants are checked against the oracle in the tests.
@@ -1492,21 +1386,6 @@ def g1_mul_glv(pts_jac: torch.Tensor, ab: torch.Tensor) -> torch.Tensor:
     return out
 
 
-def rp_fold_points_glv(ZB_jac: torch.Tensor, Y_jac: torch.Tensor, ab: torch.Tensor, S: int, L: int,
-                       out: torch.Tensor | None = None, uv: bool = False) -> torch.Tensor:
-    """G1 side of the fold with GLV weights: affine((a + b lambda)(ZB - Y)) per
-    item (or, ``uv``, its (x/y, 1/y) form for the normalised fold), one launch
-    -> [n, 16] (GPU only)."""
-    n = _rows(ab, 2)
-    assert ab.dtype == torch.int32 and _rows(ZB_jac, 24) * S == n and _rows(Y_jac, 24) * L == n and ZB_jac.is_cuda
-    P = out if out is not None else torch.empty((n, 16), dtype=torch.int32, device=ab.device)
-    assert P.shape == (n, 16) and P.is_contiguous()
-    _, s = _ctx(ZB_jac, Y_jac, ab)
-    _call("dx_rp_points_glv", s, _ptr(ZB_jac.contiguous()), _ptr(Y_jac.contiguous()), _ptr(ab.contiguous()),
-          _ptr(_glv_const("beta", ab.device)), _ptr(P), n, S, L, int(uv))
-    return P
-
-
 def g1_aff_to_uv_(aff: torch.Tensor) -> torch.Tensor:
     """In place: affine (x, y) rows -> (x/y, 1/y) (infinity stays zeros)."""
     g, s = _ctx(aff)
@@ -1514,52 +1393,49 @@ def g1_aff_to_uv_(aff: torch.Tensor) -> torch.Tensor:
     return aff
 
 
-def rp_fold_ncoeffs(V_aff: torch.Tensor, variant: str | None = None) -> torch.Tensor:
-    """Normalised shared-V line image: per V and step (c1/c0, c3/c0) ->
-    flat int32 [steps * 8 * m * 4] (fold mode 4, csrc/kernels/fold_body.h)."""
-    v = variant or FOLD_VARIANT
+FOLD_P_ALIGN = 8  # verifier blocks are padded to 64 K * 8 items (XCD-paired block mapping)
+
+
+def rp_fold_ncoeffs(V_aff: torch.Tensor) -> torch.Tensor:
+    """Normalised line image of every V's Miller loop (no P): per V and step
+    (c1/c0, c3/c0) -> flat int32 [steps * 8 * m * 4] (csrc/kernels/dx_fold.hip).
+    GPU only."""
     m = _rows(V_aff, 32)
     assert V_aff.is_cuda and V_aff.is_contiguous()
-    steps = getattr(_load(), f"dx_fold_steps_{v}")()
+    steps = _load().dx_fold_steps()
     img = torch.empty((steps * 8 * m * 4,), dtype=torch.int32, device=V_aff.device)
     scratch = torch.empty((2 * steps * 4 * m * 4,), dtype=torch.int32, device=V_aff.device)
     _, s = _ctx(V_aff)
-    rc = _raw_call(f"dx_rp_ncoeffs_{v}", s, _ptr(V_aff), _ptr(img), _ptr(scratch), m)
-    if rc:
-        raise RuntimeError(f"dx_rp_ncoeffs_{v} failed rc={rc}")
+    _call("dx_rp_ncoeffs", s, _ptr(V_aff), _ptr(img), _ptr(scratch), m)
     return img
 
 
-def rp_fold_accum_n(img: torch.Tensor, UV: torch.Tensor, V_aff: torch.Tensor, period: int, G: int, K: int = 4,
-                    variant: str | None = None) -> torch.Tensor:
-    """Normalised shared-V accumulation: G verifiers' (u, v) point images
-    against one normalised line image -> [G * period / (64 K), 96]."""
-    v = variant or FOLD_VARIANT
+def rp_fold_accum_n(img: torch.Tensor, UV: torch.Tensor, V_aff: torch.Tensor, period: int, G: int,
+                    K: int = 4) -> torch.Tensor:
+    """One-lane normalised accumulation: G verifiers' (u, v) point images
+    (UV[v * period + q], q < m) against one normalised line image, K items
+    per lane sharing one accumulator -> [G * period / (64 K), 96] partial
+    products, verifier-major."""
     m = _rows(V_aff, 32)
     assert _rows(UV, 16) == G * period and period >= m and period % (64 * K * FOLD_P_ALIGN) == 0
-    steps = getattr(_load(), f"dx_fold_steps_{v}")()
-    assert img.numel() == steps * 8 * m * 4
+    assert img.numel() == _load().dx_fold_steps() * 8 * m * 4
     fb = torch.empty((G * period // (64 * K), 96), dtype=torch.int32, device=UV.device)
     _, s = _ctx(img, UV, V_aff)
-    rc = _raw_call(f"dx_rp_accum_n_{v}", s, _ptr(img), _ptr(UV), _ptr(V_aff), _ptr(fb), m, period, G, K)
-    if rc:
-        raise RuntimeError(f"dx_rp_accum_n_{v} failed rc={rc}")
+    _call("dx_rp_accum_n", s, _ptr(img), _ptr(UV), _ptr(V_aff), _ptr(fb), m, period, G, K)
     return fb
 
 
 def rp_fold_accum_coop_raw(coef: torch.Tensor, P_aff: torch.Tensor, V_aff: torch.Tensor, period: int,
                            G: int) -> torch.Tensor:
-    """``rp_fold_accum_coop`` over the RAW line coefficients (``rp_fold_coeffs``,
+    """Three-lane accumulation over the RAW line coefficients (``rp_fold_coeffs``,
     no normalising pass) and affine points P -> [G * period / 64, 96].  GPU only."""
     m = _rows(V_aff, 32)
     n = G * period
     assert _rows(P_aff, 16) == n and period >= m and period % 64 == 0
-    assert coef.numel() == _load().dx_ufold_coop_steps() * 12 * m * 4
+    assert coef.numel() == _load().dx_fold_steps() * 12 * m * 4  # one step count (pairing.h) sizes both folds' images
     f = torch.empty((n, 96), dtype=torch.int32, device=P_aff.device)
     _, s = _ctx(coef, P_aff, V_aff)
-    rc = _raw_call("dx_ufold_coop_raw", s, _ptr(coef), _ptr(P_aff), _ptr(V_aff), _ptr(f), m, period, n)
-    if rc:
-        raise RuntimeError(f"dx_ufold_coop_raw failed rc={rc}")
+    _call("dx_ufold_coop_raw", s, _ptr(coef), _ptr(P_aff), _ptr(V_aff), _ptr(f), m, period, n)
     x = f.view(64, n // 64, 96)  # written lane-major by the kernel: item t at row (t % 64, t // 64)
     while x.shape[0] > 1:
         x = _gt_prod_level(x, 8)
@@ -1576,41 +1452,17 @@ def gt_frob8(a: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
     return out
 
 
-def rp_fold_coeffs(V_aff: torch.Tensor, variant: str | None = None) -> torch.Tensor:
-    """Shared-V phase 1: the line coefficients of every V's Miller loop (no P)
+def rp_fold_coeffs(V_aff: torch.Tensor) -> torch.Tensor:
+    """The raw line coefficients (c0, c1, c3) of every V's Miller loop (no P)
     -> flat int32 image [steps * 12 * m * 4]; several verifiers folding the
-    same proofs share it (``rp_fold_accum_p`` evaluates at their P)."""
-    v = variant or FOLD_VARIANT
+    same proofs share it (``rp_fold_accum_coop_raw`` evaluates at their P).
+    GPU only."""
     m = _rows(V_aff, 32)
     assert V_aff.is_cuda and V_aff.is_contiguous()
-    steps = getattr(_load(), f"dx_fold_steps_{v}")()
-    coef = torch.empty((steps * 12 * m * 4,), dtype=torch.int32, device=V_aff.device)
+    coef = torch.empty((_load().dx_fold_steps() * 12 * m * 4,), dtype=torch.int32, device=V_aff.device)
     _, s = _ctx(V_aff)
-    rc = _raw_call(f"dx_rp_coeffs_{v}", s, _ptr(V_aff), _ptr(coef), m)
-    if rc:
-        raise RuntimeError(f"dx_rp_coeffs_{v} failed rc={rc}")
+    _call("dx_rp_coeffs", s, _ptr(V_aff), _ptr(coef), m)
     return coef
-
-
-FOLD_P_ALIGN = 8  # verifier blocks are padded to 64 K * 8 items (XCD-paired block mapping)
-
-
-def rp_fold_accum_p(coef: torch.Tensor, P_aff: torch.Tensor, V_aff: torch.Tensor, period: int, G: int, K: int = 4,
-                    variant: str | None = None) -> torch.Tensor:
-    """Shared-V phase 2: G verifiers' point images (P[v * period + q], q < m)
-    folded against one coefficient image -> [G * period / (64 K), 96]
-    partial products, verifier-major."""
-    v = variant or FOLD_VARIANT
-    m = _rows(V_aff, 32)
-    assert _rows(P_aff, 16) == G * period and period >= m and period % (64 * K * FOLD_P_ALIGN) == 0
-    steps = getattr(_load(), f"dx_fold_steps_{v}")()
-    assert coef.numel() == steps * 12 * m * 4
-    fb = torch.empty((G * period // (64 * K), 96), dtype=torch.int32, device=P_aff.device)
-    _, s = _ctx(coef, P_aff, V_aff)
-    rc = _raw_call(f"dx_rp_accum_p_{v}", s, _ptr(coef), _ptr(P_aff), _ptr(V_aff), _ptr(fb), m, period, G, K)
-    if rc:
-        raise RuntimeError(f"dx_rp_accum_p_{v} failed rc={rc}")
-    return fb
 
 
 def gt_slice_prod(src: torch.Tensor, idx, start: torch.Tensor, length: torch.Tensor) -> torch.Tensor:
@@ -1649,11 +1501,6 @@ def _segment_passes(counts):
         passes.append((start, ln))
         c = n_sl
     return passes
-
-
-def _multi_exp64_plan(rho: torch.Tensor):
-    """Bucket plan of prod_i a_i^{rho_i} for 64-bit exponents (limbs 0, 1 of rho)."""
-    return _bucket_plan(rho, _ME_W)
 
 
 def _sort_buckets(keys: torch.Tensor, items: torch.Tensor, nb: int):
@@ -1709,32 +1556,6 @@ def _segment_passes_dev(counts, dev, first_slice: int | None = None):
     return passes
 
 
-def _segment_passes_dev_torch(counts, dev, first_slice: int | None = None):
-    """``_segment_passes`` with the per-slice (start, len) arrays built on the
-    device: only the per-bucket counts (at most a few thousand) live on the
-    host, the millions of slice descriptors of a wide multi-exponentiation
-    never cross PCIe and never run through numpy.  ``first_slice``: entries
-    per thread in the first pass (later passes use _ME_SLICE)."""
-    import numpy as _np
-
-    passes = []
-    c = _np.asarray(counts, dtype=_np.int64)
-    while c.size and c.max() > 1:
-        sl = first_slice if (first_slice and not passes) else _ME_SLICE
-        n_sl = (c + sl - 1) // sl
-        total = int(n_sl.sum())
-        ct = _upload(c, dev)
-        nt_ = _upload(n_sl, dev)
-        first = torch.cumsum(ct, 0) - ct
-        b = torch.repeat_interleave(torch.arange(c.size, device=dev), nt_, output_size=total)
-        k = torch.arange(total, device=dev) - (torch.cumsum(nt_, 0) - nt_)[b]
-        start = first[b] + k * sl
-        ln = torch.minimum(ct[b] - k * sl, torch.full_like(k, sl)).to(torch.int32)
-        passes.append((start.contiguous(), ln.contiguous()))
-        c = n_sl
-    return passes
-
-
 def _group_arg(group, n: int, dev):
     """(explicit int32 group tensor or None, group stride): an int ``group``
     means entry t belongs to group t // group (no per-entry tensor)."""
@@ -1773,33 +1594,6 @@ def _bucket_plan(k: torch.Tensor, W: int, group: torch.Tensor | None = None, n_g
     slot = torch.from_numpy((bk & mask) * W + (bk >> c))
     return {"item": it, "passes": passes, "bk": bk, "single": not passes,
             "digit_sc": _upload(sc.numpy(), dev), "slot": _upload(slot.numpy(), dev), "W": W, "c": c}
-
-
-def _multi_exp64_run(a: torch.Tensor, plan) -> torch.Tensor:
-    """Finish prod a_i^{rho_i}: segmented passes -> bucket values B_{w,d} ->
-    B^d (GPU), then per-window products and the 8-window Horner combination
-    on the host (short serial Fp12 chains: one host core beats one GPU lane)."""
-    dev = a.device
-    bk = plan["bk"]
-    if bk.size == 0:
-        return gt_one("cpu").clone()
-    cur = a.index_select(0, plan["item"]).contiguous() if plan["single"] else None
-    for k, (st, ln) in enumerate(plan["passes"]):
-        cur = gt_slice_prod(a if k == 0 else cur, plan["item"] if k == 0 else None, st, ln)
-    bkp = gt_pow(cur, plan["digit_sc"])
-    W, c = plan.get("W", _ME_W), plan.get("c", _ME_C)
-    win = gt_one(dev).repeat((1 << c) * W, 1)
-    win[plan["slot"]] = bkp
-    win = win.view(1 << c, W, 96)
-    if dev.type == "cuda":
-        while win.shape[0] > 32:
-            win = _gt_prod_level(win, 8)
-    S_w = gt_prod(win.cpu(), chunk=4)                                  # [W, 96] on the host
-    acc = S_w[W - 1: W].contiguous()
-    for w in range(W - 2, -1, -1):
-        acc = gt_pow(acc, _pow2_scalar(c))
-        acc = gt_mul(acc, S_w[w: w + 1].contiguous())
-    return acc
 
 
 def multi_exp_plan(k: torch.Tensor, group, n_groups: int, W: int = _ME_W, c: int = 8):
@@ -2319,16 +2113,6 @@ def g2_chunk_weight(B_jac: torch.Tensor, d: torch.Tensor, start: torch.Tensor, l
     g, s = _ctx(B_jac, d, start, length, base)
     _call("dx_g2_chunk_weight", g, s, _ptr(B_jac.contiguous()), _ptr(d.contiguous()), _ptr(start), _ptr(length),
           _ptr(base), _ptr(out), n)
-    return out
-
-
-def g2_mul_small(jac: torch.Tensor, d: torch.Tensor) -> torch.Tensor:
-    """d[i] * jac[i] (Jacobian G2, 0 <= d < 2^31)."""
-    n = _rows(jac, 48)
-    assert d.dtype == torch.int32 and d.numel() == n
-    out = torch.empty_like(jac)
-    g, s = _ctx(jac, d)
-    _call("dx_g2_mul_small", g, s, _ptr(jac.contiguous()), _ptr(d.contiguous()), _ptr(out), n)
     return out
 
 

@@ -258,9 +258,17 @@ def test_every_operation_on_gpu(gpu_device, tmp_path, op):
     node.close(remove=True)
 
 
-def test_two_phase_fold_matches_oracle(gpu_device, variant="inl"):
-    """Line image + K-item multi-Miller accumulation == product of the
-    oracle's pairings (after one final exponentiation), for every K."""
+def _fold_period(m, rows):
+    """The smallest multiple of rows * FOLD_P_ALIGN that holds m items."""
+    step = rows * nt.FOLD_P_ALIGN
+    return -(-m // step) * step
+
+
+def test_two_phase_fold_matches_oracle(gpu_device):
+    """The verifier's two U-side folds == product of the oracle's pairings
+    (after one final exponentiation): the normalised coefficient image + K-item
+    multi-Miller accumulation for every K, and the raw coefficient image +
+    three-lane accumulation."""
     m = 67  # a ragged last workgroup for every K
     ks = [RNG.randrange(1, O.R) for _ in range(m)]
     kq = [RNG.randrange(1, O.R) for _ in range(m)]
@@ -271,11 +279,22 @@ def test_two_phase_fold_matches_oracle(gpu_device, variant="inl"):
     gT = O.pairing(O.G1_GEN, O.G2_GEN)
     expo = sum(a * b for i, (a, b) in enumerate(zip(ks, kq)) if i != 5) % O.R
     want = gT ** expo
-    lines = nt.rp_fold_lines(P, V, variant)
+
+    def padded(period):
+        Pp = torch.zeros((period, 16), dtype=torch.int32, device=gpu_device)
+        Pp[:m] = P
+        return Pp
+
+    img = nt.rp_fold_ncoeffs(V)
     for K in (1, 2, 4, 8):
-        fb = nt.rp_fold_accum(lines, m, K, variant)
+        period = _fold_period(m, 64 * K)
+        fb = nt.rp_fold_accum_n(img, nt.g1_aff_to_uv_(padded(period)), V, period, 1, K)
         got = nt.final_exp(nt._finish_prod_on_host(fb))
         assert bn.gt_from_tensor(got)[0] == want, K
+    period = _fold_period(m, 64)
+    fb = nt.rp_fold_accum_coop_raw(nt.rp_fold_coeffs(V), padded(period), V, period, 1)
+    got = nt.final_exp(nt._finish_prod_on_host(fb))
+    assert bn.gt_from_tensor(got)[0] == want, "coop"
 
 
 def test_fb4_combs_match_oracle(gpu_device):
@@ -319,22 +338,6 @@ def test_range_prover_layouts_gpu(gpu_device, bits, monkeypatch):
     assert not rp.verify_range_proof_list(rpl, sm, P, 1.0, gpu_device)
 
 
-def test_fold_points_match_g1_ops(gpu_device, variant="inl"):
-    """Fused gather + difference + 64-bit multiplication + affine == the same
-    through the separate G1 launches (including Y = infinity rows)."""
-    S, L, npj = 3, 4, 5
-    ZB = nt.g1_fb_mul(bn.base_table(gpu_device), bn.random_scalars(npj * L, gpu_device))
-    Y = nt.g1_fb_mul(bn.base_table(gpu_device), bn.random_scalars(npj * S, gpu_device))
-    Y[2] = bn.g1_infinity_jac(1, gpu_device)[0]
-    rho = bn.random_scalars(npj * S * L, gpu_device)
-    rho[:, 2:] = 0
-    got = nt.rp_fold_points(ZB, Y, rho, S, L, variant)
-    zb = ZB.view(npj, 1, L, 24).expand(npj, S, L, 24).reshape(-1, 24).contiguous()
-    yy = Y.view(npj, S, 1, 24).expand(npj, S, L, 24).reshape(-1, 24).contiguous()
-    want = nt.g1_to_affine(nt.g1_mul(nt.g1_add(zb, yy, subtract=True), rho))
-    assert torch.equal(got, want)
-
-
 def test_int_moments_gpu_matches_host(gpu_device):
     """K14 on gfx950 vs the host path: one 1e5-record DP split over many
     workgroups, thousands of one-record DPs, empty DPs, and the widest pair
@@ -372,30 +375,6 @@ def test_batched_dp_encoding_gpu(gpu_device, tmp_path):
         node.close(remove=True)
 
 
-@pytest.mark.parametrize("K", [1, 8])
-def test_shared_v_fold_infinities(gpu_device, K):
-    """Shared-V coefficients + per-verifier evaluation: items whose P or V is
-    the point at infinity contribute 1, as in the per-item line image."""
-    m, G = 700, 2
-    period = -(-m // (64 * K * nt.FOLD_P_ALIGN)) * 64 * K * nt.FOLD_P_ALIGN
-    V = nt.g2_fb_mul(bn.base2_table(gpu_device), bn.random_scalars(m, gpu_device))
-    V[5] = 0
-    V[640] = 0
-    P = torch.zeros((G * period, 16), dtype=torch.int32, device=gpu_device)
-    for v in range(G):
-        Pv = nt.g1_to_affine(nt.g1_fb_mul(bn.base_table(gpu_device), bn.random_scalars(m, gpu_device)))
-        Pv[3 + v] = 0
-        P[v * period: v * period + m] = Pv
-    fb = nt.rp_fold_accum_p(nt.rp_fold_coeffs(V), P, V, period, G, K)
-    blk = period // (64 * K)
-    for v in range(G):
-        Pv = P[v * period: v * period + m].contiguous()
-        alone = nt.rp_fold_accum(nt.rp_fold_lines(Pv, V), m, 1)
-        a = nt.final_exp(nt._finish_prod_on_host(fb[v * blk:(v + 1) * blk]))
-        b = nt.final_exp(nt._finish_prod_on_host(alone))
-        assert bool(nt.gt_eq(a, b).all()), v
-
-
 def test_gpu_ops_match_oracle(gpu_device):
     """GT exponentiation, G2 scalar multiplication and the G1 MSM on gfx950
     against the pure-Python oracle (not the native host path)."""
@@ -419,43 +398,60 @@ def test_gpu_ops_match_oracle(gpu_device):
 
 
 def test_glv_points_match_host(gpu_device):
-    """GLV point kernel == affine((a + b lambda)(ZB - Y)) computed with the
-    host path's full-scalar multiplication, incl. T at infinity."""
+    """GLV ladder kernel (g1_mul_glv) on T = ZB - Y == (a + b lambda) T computed
+    with the host path's full-scalar multiplication, incl. T at infinity."""
     S, L, npj = 2, 3, 9
     ZB = nt.g1_fb_mul(bn.base_table(gpu_device), bn.random_scalars(npj * L, gpu_device))
     Y = nt.g1_fb_mul(bn.base_table(gpu_device), bn.random_scalars(npj * S, gpu_device))
     Y[1] = ZB[0]  # T = ZB - Y = infinity for every item of (p=0, i=1, j=0)
     m = npj * S * L
     ab, rho = nt.glv_weights(m, gpu_device)
-    got = nt.rp_fold_points_glv(ZB, Y, ab, S, L).cpu()
     zb = ZB.cpu().view(npj, 1, L, 24).expand(npj, S, L, 24).reshape(-1, 24).contiguous()
     yy = Y.cpu().view(npj, S, 1, 24).expand(npj, S, L, 24).reshape(-1, 24).contiguous()
     T = nt.g1_add(zb, yy, subtract=True)
+    got = nt.g1_to_affine(nt.g1_mul_glv(T.to(gpu_device), ab)).cpu()
     exp = nt.g1_to_affine(nt.g1_mul(T, rho.cpu()))
     assert torch.equal(got, exp)
 
 
-@pytest.mark.parametrize("K", [1, 8])
-def test_normalised_fold_matches_shared_v(gpu_device, K):
-    """Fold mode 4 (lines normalised to 1 + (a u) w + (b v) w^3) == mode 3
-    after the final exponentiation, with points / V at infinity."""
+@pytest.fixture(scope="module")
+def fold_case(gpu_device):
+    """One shared V image (m = 700, rows 5, 7 and 640 at infinity), G = 2
+    verifiers' affine points (rows 3 + v and 11 + v at infinity) and per
+    verifier FE(prod_q ML(P_vq, V_q)) from the per-item Miller loops
+    (nt.miller_loop: against the oracle in test_pairing_gpu_matches_oracle)."""
     m, G = 700, 2
-    period = -(-m // (64 * K * nt.FOLD_P_ALIGN)) * 64 * K * nt.FOLD_P_ALIGN
     V = nt.g2_fb_mul(bn.base2_table(gpu_device), bn.random_scalars(m, gpu_device))
-    V[7] = 0
-    P = torch.zeros((G * period, 16), dtype=torch.int32, device=gpu_device)
+    V[5] = V[7] = V[640] = 0
+    Ps, want = [], []
     for v in range(G):
         Pv = nt.g1_to_affine(nt.g1_fb_mul(bn.base_table(gpu_device), bn.random_scalars(m, gpu_device)))
-        Pv[11 + v] = 0
-        P[v * period: v * period + m] = Pv
-    ref = nt.rp_fold_accum_p(nt.rp_fold_coeffs(V), P, V, period, G, K)
-    UV = nt.g1_aff_to_uv_(P.clone())
-    got = nt.rp_fold_accum_n(nt.rp_fold_ncoeffs(V), UV, V, period, G, K)
+        Pv[3 + v] = Pv[11 + v] = 0
+        ml = nt.miller_loop(Pv, V)
+        dead = [5, 7, 640, 3 + v, 11 + v]  # P or V at infinity: the item's Miller value is one
+        assert torch.equal(ml[dead], nt.gt_one(gpu_device).expand(len(dead), 96))
+        Ps.append(Pv)
+        want.append(nt.final_exp(nt._finish_prod_on_host(ml)))
+    return {"m": m, "G": G, "V": V, "P": Ps, "want": want}
+
+
+@pytest.mark.parametrize("K", [1, 2, 4, 8])
+def test_normalised_fold_infinities(gpu_device, fold_case, K):
+    """Normalised coefficient image (lines 1 + (a u) w + (b v) w^3) shared by G
+    verifiers + K-item accumulation == each verifier's product of per-item
+    Miller loops after the final exponentiation; items whose P or V is the
+    point at infinity contribute 1."""
+    c = fold_case
+    m, G, V = c["m"], c["G"], c["V"]
+    period = _fold_period(m, 64 * K)
+    P = torch.zeros((G * period, 16), dtype=torch.int32, device=gpu_device)
+    for v in range(G):
+        P[v * period: v * period + m] = c["P"][v]
+    got = nt.rp_fold_accum_n(nt.rp_fold_ncoeffs(V), nt.g1_aff_to_uv_(P), V, period, G, K)
     blk = period // (64 * K)
     for v in range(G):
         a = nt.final_exp(nt._finish_prod_on_host(got[v * blk:(v + 1) * blk]))
-        b = nt.final_exp(nt._finish_prod_on_host(ref[v * blk:(v + 1) * blk]))
-        assert bool(nt.gt_eq(a, b).all()), v
+        assert bool(nt.gt_eq(a, c["want"][v]).all()), v
 
 
 def test_ufold_coop_matches_one_lane(gpu_device):

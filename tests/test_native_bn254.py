@@ -109,7 +109,7 @@ def test_random_scalars_in_range():
     assert all(0 < v < O.R for v in s) and len(set(s)) == 500
 
 
-def test_gt_bucket_multi_exp64_matches_direct():
+def test_gt_bucket_multi_exp_grouped_matches_direct():
     """prod a_i^{rho_i} (64-bit rho) through the bucket plan == per-item powers."""
     import os
 
@@ -121,7 +121,7 @@ def test_gt_bucket_multi_exp64_matches_direct():
     rho = torch.zeros((n, 8), dtype=torch.int32)
     rho[:, :2] = torch.from_numpy(np.frombuffer(os.urandom(8 * n), dtype="<i4").reshape(n, 2).copy())
     rho[:7, :2] = 0  # all-zero digits: items contribute nothing
-    got = nt._multi_exp64_run(a, nt._multi_exp64_plan(rho))
+    got = nt.multi_exp_grouped_finish(nt.multi_exp_grouped(a, rho, None, 1))
     ref = nt.gt_prod(nt.gt_pow(a, rho).view(-1, 1, 96), chunk=4).view(1, 96)
     assert torch.equal(got, ref)
 

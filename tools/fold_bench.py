@@ -1,8 +1,11 @@
 #!/usr/bin/env python3
-"""Microbenchmark + check of the range-verification Miller fold variants on
-one GPU: the fused per-item kernel (dx_rp_verify_fold) vs the two-phase fold
-(lines + K-item multi-Miller accumulation, out-of-line / inlined tower).
-Prints one JSON line per variant with ms and Miller loops/s."""
+"""Microbenchmark + check of the verifier's U-side Miller folds on one GPU:
+the coefficient images (raw and normalised), the one-lane K-item accumulation
+over the normalised image and the three-lane accumulation over the raw one.
+Each fold is first checked against per-item Miller loops on a 4096-item
+prefix.  Prints one JSON line per section with ms and Miller loops/s.
+
+Usage: python tools/fold_bench.py [items]   (FOLD_G: verifiers sharing the image)"""
 import json
 import os
 import sys
@@ -13,9 +16,6 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from drynx_amd import native as nt  # noqa: E402
 from drynx_amd.crypto import bn254 as bn  # noqa: E402
-
-
-VARIANTS = os.environ.get("FOLD_VARIANTS", "inl").split(",")
 
 
 def timed(fn, reps=3):
@@ -30,70 +30,58 @@ def timed(fn, reps=3):
     return best, out
 
 
+def padded(P, n, rows, G, dev):
+    """G copies of the n points, each padded to a whole number of rows * FOLD_P_ALIGN items."""
+    per = rows * nt.FOLD_P_ALIGN
+    pad = -(-n // per) * per
+    PG = torch.zeros((G * pad, 16), dtype=torch.int32, device=dev)
+    for g in range(G):
+        PG[g * pad: g * pad + n] = P[:n]
+    return PG, pad
+
+
 def main():
     n = int(sys.argv[1]) if len(sys.argv) > 1 else 993_600
+    G = int(os.environ.get("FOLD_G", "3"))
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
-    k1 = bn.random_scalars(n, dev)
-    k2 = bn.random_scalars(n, dev)
-    P = nt.g1_to_affine(nt.g1_fb_mul(bn.base_table(dev), k1))
-    V = nt.g2_fb_mul(bn.base2_table(dev), k2)
+    P = nt.g1_to_affine(nt.g1_fb_mul(bn.base_table(dev), bn.random_scalars(n, dev)))
+    V = nt.g2_fb_mul(bn.base2_table(dev), bn.random_scalars(n, dev))
     # reference value on a small prefix: FE(prod ML) via per-item Miller loops
-    m = 4096
-    ref = nt.final_exp(nt._finish_prod_on_host(nt.miller_loop(P[:m].contiguous(), V[:m].contiguous())))
-    for v in VARIANTS:
-        for K in (1, 2, 4, 8):
-            fb = nt.rp_fold_accum(nt.rp_fold_lines(P[:m].contiguous(), V[:m].contiguous(), v), m, K, v)
-            got = nt.final_exp(nt._finish_prod_on_host(fb))
-            assert bool(nt.gt_eq(got, ref).all()), (v, K)
+    m = min(n, 4096)
+    Vm = V[:m].contiguous()
+    ref = nt.final_exp(nt._finish_prod_on_host(nt.miller_loop(P[:m].contiguous(), Vm)))
+
+    def check(fb, what):
+        got = nt.final_exp(nt._finish_prod_on_host(fb))
+        assert bool(nt.gt_eq(got, ref).all()), what
+
+    img = nt.rp_fold_ncoeffs(Vm)
+    for K in (1, 2, 4, 8):
+        PG, pad = padded(P, m, 64 * K, 1, dev)
+        check(nt.rp_fold_accum_n(img, nt.g1_aff_to_uv_(PG), Vm, pad, 1, K), ("normalised", K))
+    PG, pad = padded(P, m, 64, 1, dev)
+    check(nt.rp_fold_accum_coop_raw(nt.rp_fold_coeffs(Vm), PG, Vm, pad, 1), "coop")
+    del img, PG
     print(json.dumps({"check": "ok", "items": m}), flush=True)
-    # the fused kernel (with its own rho * (ZB - Y) point work): rho = 1, Y = 0
-    ZB = nt.g1_from_affine(P)
-    Y = bn.g1_infinity_jac(n, dev)
-    rho = torch.zeros((n, 8), dtype=torch.int32, device=dev)
-    rho[:, 0] = 1
-    if os.environ.get("FOLD_FUSED", "0") == "1":
-        t, _ = timed(lambda: nt.rp_verify_fold(ZB, Y, rho, V, 1, 1))
-        print(json.dumps({"variant": "fused", "n": n, "ms": round(1e3 * t, 2), "ml_per_s": round(n / t)}), flush=True)
-    for v in VARIANTS:
-        tl, lines = timed(lambda: nt.rp_fold_lines(P, V, v))
-        for K in (1, 2, 4, 8):
-            ta, _ = timed(lambda: nt.rp_fold_accum(lines, n, K, v))
-            print(json.dumps({"variant": v, "K": K, "n": n, "lines_ms": round(1e3 * tl, 2),
-                              "accum_ms": round(1e3 * ta, 2),
-                              "ml_per_s": round(n / (tl + ta))}), flush=True)
-        del lines
-        torch.cuda.empty_cache()
-        # shared-V: one coefficient image, G verifiers' points evaluated in the accumulation
-        G = int(os.environ.get("FOLD_G", "3"))
-        tc, coef = timed(lambda: nt.rp_fold_coeffs(V, v))
-        for K in (4, 8):
-            per = 64 * K * nt.FOLD_P_ALIGN
-            pad = -(-n // per) * per
-            PG = torch.zeros((G * pad, 16), dtype=torch.int32, device=dev)
-            for g in range(G):
-                PG[g * pad: g * pad + n] = P
-            ta, _ = timed(lambda: nt.rp_fold_accum_p(coef, PG, V, pad, G, K, v))
-            print(json.dumps({"variant": v + "-sharedV", "G": G, "K": K, "n": n, "coeffs_ms": round(1e3 * tc, 2),
-                              "accum_ms": round(1e3 * ta, 2), "ml_per_s": round(G * n / (tc + ta))}), flush=True)
-            del PG
-        del coef
-        torch.cuda.empty_cache()
-        # normalised lines (fold mode 4): (c1/c0, c3/c0) per V, (x/y, 1/y) per point
-        tn, img = timed(lambda: nt.rp_fold_ncoeffs(V, v))
-        for K in (4, 8):
-            per = 64 * K * nt.FOLD_P_ALIGN
-            pad = -(-n // per) * per
-            UV = torch.zeros((G * pad, 16), dtype=torch.int32, device=dev)
-            uv1 = nt.g1_aff_to_uv_(P.clone())
-            for g in range(G):
-                UV[g * pad: g * pad + n] = uv1
-            ta, _ = timed(lambda: nt.rp_fold_accum_n(img, UV, V, pad, G, K, v))
-            print(json.dumps({"variant": v + "-normalised", "G": G, "K": K, "n": n, "coeffs_ms": round(1e3 * tn, 2),
-                              "accum_ms": round(1e3 * ta, 2), "ml_per_s": round(G * n / (tn + ta))}), flush=True)
-            del UV
-        del img
-        torch.cuda.empty_cache()
+
+    # raw coefficients + three lanes per item (the pool-slice path)
+    tc, coef = timed(lambda: nt.rp_fold_coeffs(V))
+    PG, pad = padded(P, n, 64, G, dev)
+    ta, _ = timed(lambda: nt.rp_fold_accum_coop_raw(coef, PG, V, pad, G))
+    print(json.dumps({"fold": "coop-raw", "G": G, "n": n, "coeffs_ms": round(1e3 * tc, 2),
+                      "accum_ms": round(1e3 * ta, 2), "ml_per_s": round(G * n / (tc + ta))}), flush=True)
+    del coef, PG
+    torch.cuda.empty_cache()
+    # normalised lines: (c1/c0, c3/c0) per V, (x/y, 1/y) per point, K items per lane
+    tn, img = timed(lambda: nt.rp_fold_ncoeffs(V))
+    for K in (1, 2, 4, 8):
+        PG, pad = padded(P, n, 64 * K, G, dev)
+        UV = nt.g1_aff_to_uv_(PG)
+        ta, _ = timed(lambda: nt.rp_fold_accum_n(img, UV, V, pad, G, K))
+        print(json.dumps({"fold": "normalised", "G": G, "K": K, "n": n, "coeffs_ms": round(1e3 * tn, 2),
+                          "accum_ms": round(1e3 * ta, 2), "ml_per_s": round(G * n / (tn + ta))}), flush=True)
+        del PG, UV
 
 
 if __name__ == "__main__":
