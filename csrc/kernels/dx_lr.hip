@@ -11,15 +11,26 @@
 // (O(N (d+1)^2) scalar float ops in Go, after a separate standardisation pass,
 // :367-403).  Here it is one tall-skinny GEMM over the records: K = N is the
 // reduction dimension of v_mfma_f64_16x16x4f64.  For one K-step of 4 records,
-// lane l holds xa[k][16t + (l&15)] (k = l>>4) for the three 16-column tiles t;
-// the same registers are the B operand and, scaled by w[k], the A operand, so
-// the 3x3 output tiles need 3 loads + 9 MFMAs per step.  The level-1 vector
-// rides in the A operand's spare column D (A = g_i there, B = 0), so it costs
-// no extra pass over HBM (it used to be a separate rocBLAS gemv that ran on a
-// single workgroup).  Waves stride over records (grid-stride), the 4 waves of
-// a block reduce through LDS and each block writes one 48x48 partial; a tiny
-// second pass (dx_lr_reduce: fixed summation order over the [blocks,48,48]
-// slab, batched over the DPs of a rank) finishes deterministically.
+// lane l holds xa[k][16t + (l&15)] (k = l>>4) for every 16-column tile t it
+// works on; the same registers are the B operand and, scaled by w[k], the A
+// operand.
+//
+// The output is cut into tile-blocks of at most 3x3 tiles (48x48): block
+// (x, y, z) of a launch handles record block x and tile-block (y, z), loads the TA
+// A-side and TB B-side tiles of its tile-block (the same registers on a
+// diagonal tile-block) and issues TA*TB MFMAs per step.  Up to 48 rows
+// (level 2 plus the level-1 row) are ONE 3x3 tile-block at offset 0, exactly
+// the kernel this used to be; wider inputs take a grid of 3x3 tile-blocks
+// plus narrower instantiations on the ragged right/bottom edge, so tiles that
+// are entirely padding are never computed.  The level-1 vector rides in the A
+// operand's spare row D (A = g_i there, B as usual) of whichever tile-block
+// row holds global row D, so it costs no extra pass over HBM (it used to be a
+// separate rocBLAS gemv that ran on a single workgroup).  Waves stride over
+// records (grid-stride), the 4 waves of a block reduce through LDS and each
+// block writes its sub-block of a PxP partial (P = 48, or the tile-padded row
+// count beyond that); a tiny second pass (dx_lr_reduce: fixed summation order
+// over the [blocks,P,P] slab, batched over the DPs of a rank) finishes
+// deterministically.
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <cstdio>
@@ -29,7 +40,7 @@ typedef double dx_f64x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 constexpr int kTile = 16;
-constexpr int kTiles = 3;  // D <= 48
+constexpr int kTiles = 3;  // a tile-block is at most kTiles x kTiles tiles
 constexpr int kD = kTile * kTiles;
 constexpr int kWaves = 4;
 
@@ -47,28 +58,49 @@ struct LrArgs {
   int level1;          // 1: g = 2y - 1 accumulated in row D
 };
 
-__global__ void __launch_bounds__(256) lr_encode_kernel(LrArgs p, double *__restrict__ partial) {
+// Where one launch's tile-blocks sit in the PxP output: block (x, y, z) covers
+// row tiles ta0 + TA * y .. and column tiles tb0 + TB * z .. of record block x.
+struct LrGrid {
+  int ta0, tb0;
+  int P;  // padded output width (row stride of a partial)
+};
+
+// kDiag: every tile-block of the launch is on the diagonal (the single 3x3
+// tile-block of a narrow input): no B-side state at all.
+template <int TA, int TB, bool kDiag>
+__global__ void __launch_bounds__(256) lr_encode_kernel(LrArgs p, double *__restrict__ partial, LrGrid g) {
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
   const int col = lane & 15;
   const int kk = lane >> 4;  // 0..3 record within the K-step
   const int D = p.dx + p.aug;
-  dx_f64x4 acc[kTiles][kTiles];
+  const int ta = g.ta0 + TA * (int)blockIdx.y;           // first row tile
+  const int tb = g.tb0 + TB * (int)blockIdx.z;           // first column tile
+  const bool diag = kDiag || (TA == TB && ta == tb);     // A-side values == B-side values
+  dx_f64x4 acc[TA][TB];
 #pragma unroll
-  for (int a = 0; a < kTiles; a++)
+  for (int a = 0; a < TA; a++)
 #pragma unroll
-    for (int b = 0; b < kTiles; b++) acc[a][b] = (dx_f64x4){0.0, 0.0, 0.0, 0.0};
+    for (int b = 0; b < TB; b++) acc[a][b] = (dx_f64x4){0.0, 0.0, 0.0, 0.0};
 
-  // per-lane standardisation constants of the three columns this lane owns
-  double mu[kTiles], sdv[kTiles];
-  int src[kTiles];
+  // per-lane standardisation constants of the row-side and column-side columns this lane owns
+  double mua[TA], sda[TA], mub[TB], sdb[TB];
+  int srca[TA], srcb[TB];
 #pragma unroll
-  for (int t = 0; t < kTiles; t++) {
-    const int c = t * kTile + col;
-    src[t] = c - p.aug;  // raw column, -1 for the augmentation column
-    const bool raw = (c < D) && src[t] >= 0;
-    mu[t] = (raw && p.mean) ? p.mean[src[t]] : 0.0;
-    sdv[t] = (raw && p.sd) ? p.sd[src[t]] : 1.0;
+  for (int t = 0; t < TA; t++) {
+    const int c = (ta + t) * kTile + col;
+    srca[t] = c - p.aug;  // raw column, -1 for the augmentation column
+    const bool raw = (c < D) && srca[t] >= 0;
+    mua[t] = (raw && p.mean) ? p.mean[srca[t]] : 0.0;
+    sda[t] = (raw && p.sd) ? p.sd[srca[t]] : 1.0;
+  }
+#pragma unroll
+  for (int t = 0; t < TB; t++) {
+    const int c = (tb + t) * kTile + col;
+    srcb[t] = c - p.aug;
+    const bool raw = !diag && (c < D) && srcb[t] >= 0;
+    mub[t] = (raw && p.mean) ? p.mean[srcb[t]] : 0.0;
+    sdb[t] = (raw && p.sd) ? p.sd[srcb[t]] : 1.0;
   }
 
   const int64_t gw = (int64_t)blockIdx.x * kWaves + wave;
@@ -76,7 +108,7 @@ __global__ void __launch_bounds__(256) lr_encode_kernel(LrArgs p, double *__rest
   const int64_t steps = (p.N + 3) / 4;
   for (int64_t s = gw; s < steps; s += nw) {
     const int64_t row = s * 4 + kk;
-    double v[kTiles];
+    double va[TA], vb[TB];
     double wi = 0.0, gi = 0.0;
     if (row < p.N) {
       const double yi = p.y ? p.y[row] : 0.0;
@@ -84,46 +116,105 @@ __global__ void __launch_bounds__(256) lr_encode_kernel(LrArgs p, double *__rest
       gi = 2.0 * yi - 1.0;
       const double *xr = p.X + row * p.ldx;
 #pragma unroll
-      for (int t = 0; t < kTiles; t++) {
-        const int c = t * kTile + col;
-        if (c >= D) v[t] = 0.0;
-        else if (src[t] < 0) v[t] = 1.0;
-        else v[t] = (xr[src[t]] - mu[t]) / sdv[t];
+      for (int t = 0; t < TA; t++) {
+        const int c = (ta + t) * kTile + col;
+        if (c >= D) va[t] = 0.0;
+        else if (srca[t] < 0) va[t] = 1.0;
+        else va[t] = (xr[srca[t]] - mua[t]) / sda[t];
+      }
+      if (!diag) {
+#pragma unroll
+        for (int t = 0; t < TB; t++) {
+          const int c = (tb + t) * kTile + col;
+          if (c >= D) vb[t] = 0.0;
+          else if (srcb[t] < 0) vb[t] = 1.0;
+          else vb[t] = (xr[srcb[t]] - mub[t]) / sdb[t];
+        }
       }
     } else {
 #pragma unroll
-      for (int t = 0; t < kTiles; t++) v[t] = 0.0;
+      for (int t = 0; t < TA; t++) va[t] = 0.0;
+#pragma unroll
+      for (int t = 0; t < TB; t++) vb[t] = 0.0;
+    }
+    if (diag) {
+#pragma unroll
+      for (int t = 0; t < TB; t++) vb[t] = va[t < TA ? t : 0];
     }
 #pragma unroll
-    for (int a = 0; a < kTiles; a++) {
-      const int c = a * kTile + col;
-      const double av = (p.level1 && c == D) ? gi : v[a] * wi;
+    for (int a = 0; a < TA; a++) {
+      const int c = (ta + a) * kTile + col;  // global row of the output
+      const double av = (p.level1 && c == D) ? gi : va[a] * wi;
 #pragma unroll
-      for (int b = 0; b < kTiles; b++) acc[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, v[b], acc[a][b], 0, 0, 0);
+      for (int b = 0; b < TB; b++) acc[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, vb[b], acc[a][b], 0, 0, 0);
     }
   }
 
   // f64 16x16x4 C layout: col = lane & 15, row = (lane >> 4) + 4 * reg
-  __shared__ double red[kWaves][kD][kD];
+  constexpr int kRows = TA * kTile, kCols = TB * kTile;
+  __shared__ double red[kWaves][kRows][kCols];
 #pragma unroll
-  for (int a = 0; a < kTiles; a++)
+  for (int a = 0; a < TA; a++)
 #pragma unroll
-    for (int b = 0; b < kTiles; b++)
+    for (int b = 0; b < TB; b++)
 #pragma unroll
       for (int r = 0; r < 4; r++) red[wave][a * kTile + kk + 4 * r][b * kTile + col] = acc[a][b][r];
   __syncthreads();
-  double *out = partial + (int64_t)blockIdx.x * kD * kD;
-  for (int e = threadIdx.x; e < kD * kD; e += blockDim.x) {
-    const int i = e / kD, j = e % kD;
-    out[e] = red[0][i][j] + red[1][i][j] + red[2][i][j] + red[3][i][j];
+  double *out = partial + (int64_t)blockIdx.x * g.P * g.P + (int64_t)ta * kTile * g.P + tb * kTile;
+  for (int e = threadIdx.x; e < kRows * kCols; e += blockDim.x) {
+    const int i = e / kCols, j = e % kCols;
+    out[i * g.P + j] = red[0][i][j] + red[1][i][j] + red[2][i][j] + red[3][i][j];
   }
 }
 
-int launch(void *stream, const LrArgs &a, double *partial, int n_blocks) {
+template <int TA, int TB, bool kDiag = false>
+void launch_tiles(hipStream_t stream, const LrArgs &a, double *partial, int n_blocks, int ta0, int tb0, int nga,
+                  int ngb, int P) {
+  if (nga <= 0 || ngb <= 0) return;
+  const LrGrid g{ta0, tb0, P};
+  hipLaunchKernelGGL((lr_encode_kernel<TA, TB, kDiag>), dim3(n_blocks, nga, ngb), dim3(256), 0, stream, a, partial,
+                     g);
+}
+
+// run-time tile-block shape (tan x tbn tiles, each 1..3; 0 = nothing to launch) -> instantiation
+template <int TA>
+void launch_cols(hipStream_t stream, const LrArgs &a, double *partial, int n_blocks, int ta0, int tb0, int nga,
+                 int ngb, int P, int tbn) {
+  if (tbn == 1) launch_tiles<TA, 1>(stream, a, partial, n_blocks, ta0, tb0, nga, ngb, P);
+  else if (tbn == 2) launch_tiles<TA, 2>(stream, a, partial, n_blocks, ta0, tb0, nga, ngb, P);
+  else if (tbn == 3) launch_tiles<TA, 3>(stream, a, partial, n_blocks, ta0, tb0, nga, ngb, P);
+}
+
+void launch_rows(hipStream_t stream, const LrArgs &a, double *partial, int n_blocks, int ta0, int tb0, int nga,
+                 int ngb, int P, int tan, int tbn) {
+  if (tan == 1) launch_cols<1>(stream, a, partial, n_blocks, ta0, tb0, nga, ngb, P, tbn);
+  else if (tan == 2) launch_cols<2>(stream, a, partial, n_blocks, ta0, tb0, nga, ngb, P, tbn);
+  else if (tan == 3) launch_cols<3>(stream, a, partial, n_blocks, ta0, tb0, nga, ngb, P, tbn);
+}
+
+// Padded output width: 48 while level 2 and the level-1 row fit one 3x3
+// tile-block, the tile-padded row count beyond that.
+int lr_padded(int D, int level1) {
+  const int nt = (D + (level1 ? 1 : 0) + kTile - 1) / kTile;
+  return nt <= kTiles ? kD : nt * kTile;
+}
+
+int launch(void *stream_, const LrArgs &a, double *partial, int n_blocks, int P) {
   const int D = a.dx + a.aug;
-  if (a.dx <= 0 || D > kD || (a.level1 && D >= kD) || n_blocks <= 0) return -2;
+  if (a.dx <= 0 || n_blocks <= 0 || P != lr_padded(D, a.level1)) return -2;
   if ((a.level1 || !a.w) && !a.y) return -2;
-  hipLaunchKernelGGL(lr_encode_kernel, dim3(n_blocks), dim3(256), 0, (hipStream_t)stream, a, partial);
+  hipStream_t stream = (hipStream_t)stream_;
+  if (P == kD) {
+    launch_tiles<kTiles, kTiles, true>(stream, a, partial, n_blocks, 0, 0, 1, 1, P);
+  } else {
+    // live tiles: rows 0..D (with level 1), columns 0..D-1; full 3x3 tile-blocks, then the ragged edges
+    const int ntr = P / kTile, ntc = (D + kTile - 1) / kTile;
+    const int fa = ntr / kTiles, ra = ntr % kTiles, fb = ntc / kTiles, rb = ntc % kTiles;
+    launch_tiles<kTiles, kTiles>(stream, a, partial, n_blocks, 0, 0, fa, fb, P);
+    launch_rows(stream, a, partial, n_blocks, 0, fb * kTiles, fa, 1, P, kTiles, rb);
+    launch_rows(stream, a, partial, n_blocks, fa * kTiles, 0, 1, fb, P, ra, kTiles);
+    launch_rows(stream, a, partial, n_blocks, fa * kTiles, fb * kTiles, 1, 1, P, ra, rb);
+  }
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) {
     fprintf(stderr, "[drynx_amd native] lr_encode: %s\n", hipGetErrorString(e));
@@ -134,10 +225,11 @@ int launch(void *stream, const LrArgs &a, double *partial, int n_blocks) {
 }  // namespace
 
 // sum_i w_i X_i X_i^T over already-prepared rows (no standardisation, no level 1).
+// partial: [n_blocks][P][P], P = lr_padded(D, 0).
 extern "C" int dx_lr_moments(void *stream, const double *X, const double *w, int64_t N, int D, double *partial,
-                             int n_blocks) {
+                             int n_blocks, int P) {
   LrArgs a{X, D, N, D, 0, nullptr, nullptr, w, nullptr, 0.0, 0.0, 0};
-  return launch(stream, a, partial, n_blocks);
+  return launch(stream, a, partial, n_blocks, P);
 }
 
 // Block partials -> totals, for many encoder launches at once: out[i][e] =
@@ -184,10 +276,13 @@ extern "C" int dx_lr_reduce(void *stream, const double *partial, int64_t nb, int
 }
 
 // Fused DP encoder: standardise + augment + level-1 (row D) + level-2 ((wa*y + wb) weights).
+// partial: [n_blocks][P][P], P = lr_padded(dx + 1, 1); block columns past the
+// last live column tile (all padding) are not written.
 extern "C" int dx_lr_encode(void *stream, const double *X, int64_t ldx, int64_t N, int dx, const double *mean,
-                            const double *sd, const double *y, double wa, double wb, double *partial, int n_blocks) {
+                            const double *sd, const double *y, double wa, double wb, double *partial, int n_blocks,
+                            int P) {
   LrArgs a{X, ldx, N, dx, 1, mean, sd, nullptr, y, wa, wb, 1};
-  return launch(stream, a, partial, n_blocks);
+  return launch(stream, a, partial, n_blocks, P);
 }
 
 // Querier gradient descent for k = 2 (FindMinimumWeights, reference

@@ -15,9 +15,11 @@ Reference: lib/encoding/logistic_regression.go.
     cartesian products each iteration.
 
 MI355X design: the per-record coefficient sums are one tall-skinny fp64
-GEMM  X^T diag(w) X  over N records (K13) — the HIP MFMA kernel
-``lr_moments`` in csrc/kernels/dx_lr.hip (v_mfma_f64_16x16x4f64) when the DP's
-records live on a GPU; the CPU path uses torch float64 matmul.
+GEMM  X^T diag(w) X  over N records (K13) — the HIP MFMA kernels
+``lr_encode`` / ``lr_moments`` in csrc/kernels/dx_lr.hip (v_mfma_f64_16x16x4f64,
+a grid of up to 3x3-tile output blocks, so any number of features: the
+reference's 100-feature BC and GSE datasets included) when the DP's records
+live on a GPU; the CPU path uses torch float64 matmul.
 """
 from __future__ import annotations
 
@@ -171,8 +173,7 @@ def encode_coefficients_int_many(Xs: list, ys: list, params: LogisticRegressionP
     if not Xs or params.K > 2 or not (params.Means and params.StandardDeviations):
         return None
     d = Xs[0].shape[1] if Xs[0] is not None and Xs[0].dim() == 2 else -1
-    if d < 1 or d + 1 >= 48 or any(X is None or not X.is_cuda or X.dim() != 2 or X.shape[1] != d or len(X) == 0
-                                   for X in Xs):
+    if d < 1 or any(X is None or not X.is_cuda or X.dim() != 2 or X.shape[1] != d or len(X) == 0 for X in Xs):
         return None
     tot = nt.lr_encode_many([X.to(torch.float64).contiguous() for X in Xs], ys, params.Means,
                             params.StandardDeviations, 0.0, -1.0)
@@ -184,7 +185,7 @@ def encode_coefficients_int_many(Xs: list, ys: list, params: LogisticRegressionP
 def encode_coefficients_int(X: torch.Tensor, y: torch.Tensor, params: LogisticRegressionParameters) -> torch.Tensor:
     """The packed int64 vector the DP encrypts (before encryption)."""
     X = X.to(torch.float64)
-    if X.is_cuda and params.K <= 2 and X.shape[1] + 1 < 48:
+    if X.is_cuda and params.K <= 2:
         # one fused pass over the records: standardise + augment + level 1 + level 2 (dx_lr_encode)
         if params.Means and params.StandardDeviations:
             m = torch.as_tensor(params.Means, dtype=torch.float64)

@@ -93,13 +93,13 @@ _SIGS = {
     "dx_gt_fb_pow": [_I, _P, _P, _P, _P, _P, _L],
     "dx_gt_prod_chunks": [_I, _P, _P, _P, _L, _L, _L],
     "dx_version": [],
-    "dx_lr_moments": [_P, _P, _P, _L, _I, _P, _I],
+    "dx_lr_moments": [_P, _P, _P, _L, _I, _P, _I, _I],
     "dx_lr_gd_k2": [_P, _P, _P, _I, ctypes.c_double, ctypes.c_double, ctypes.c_double, _I, ctypes.c_double,
                     ctypes.c_double, ctypes.c_double, _P],
     "dx_random_scalars": [_I, _P, _P, ctypes.c_uint32, _P, _L],
     "dx_sha256_chunks": [_I, _P, _P, _L, _L, _P],
     "dx_hash_to_g1": [_I, _P, _P, _P, _L, _P, _L],
-    "dx_lr_encode": [_P, _P, _L, _L, _I, _P, _P, _P, ctypes.c_double, ctypes.c_double, _P, _I],
+    "dx_lr_encode": [_P, _P, _L, _L, _I, _P, _P, _P, ctypes.c_double, ctypes.c_double, _P, _I, _I],
     "dx_lr_reduce": [_P, _P, _L, _L, _L, _P],
     "dx_g1_mul_glv256": [_P, _P, _P, _P, _P, _L, _I, _I, _I],
     "dx_glv_split": [_I, _P, _P, _P, _L],
@@ -1182,15 +1182,26 @@ def sha256_rows(data: torch.Tensor, chunk: int) -> torch.Tensor:
     return out
 
 
+def _lr_padded(rows: int) -> int:
+    """Width P of the kernel's [P, P] output for `rows` live rows (level 2 plus
+    the level-1 row): 48 while they fit one 3x3 tile-block, the 16-padded row
+    count beyond that (csrc/kernels/dx_lr.hip lr_padded)."""
+    nt = (rows + 15) // 16
+    return 48 if nt <= 3 else 16 * nt
+
+
 def lr_moments(X: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
-    """sum_i w_i X_i X_i^T on the fp64-MFMA kernel (GPU tensors only)."""
-    assert X.is_cuda and X.dtype == torch.float64 and X.dim() == 2 and X.shape[1] <= 48
+    """sum_i w_i X_i X_i^T on the fp64-MFMA kernel (GPU tensors only), any
+    D = X.shape[1] >= 1."""
+    assert X.is_cuda and X.dtype == torch.float64 and X.dim() == 2 and X.shape[1] >= 1 and X.is_contiguous()
     N, D = X.shape
+    P = _lr_padded(D)
     steps = (N + 3) // 4
     n_blocks = int(max(1, min(2048, (steps + 15) // 16)))
-    partial = torch.empty((n_blocks, 48, 48), dtype=torch.float64, device=X.device)
+    partial = torch.empty((n_blocks, P, P), dtype=torch.float64, device=X.device)
     _, s = _ctx(X)
-    rc = _raw_call("dx_lr_moments", s, _ptr(X), _ptr(w.to(torch.float64).contiguous()), N, D, _ptr(partial), n_blocks)
+    rc = _raw_call("dx_lr_moments", s, _ptr(X), _ptr(w.to(torch.float64).contiguous()), N, D, _ptr(partial), n_blocks,
+                   P)
     if rc != 0:
         raise RuntimeError(f"dx_lr_moments failed rc={rc}")
     return partial.sum(0)[:D, :D]
@@ -1199,7 +1210,7 @@ def lr_moments(X: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
 def lr_encode(X: torch.Tensor, y: torch.Tensor, mean: torch.Tensor, sd: torch.Tensor, wa: float, wb: float):
     """Fused DP encoder on the fp64-MFMA kernel (GPU tensors only): with
     xa_i = [1, (X_i - mean)/sd], returns (sum_i (2y_i-1) xa_i  [D],
-    sum_i (wa*y_i + wb) xa_i xa_i^T  [D, D]), D = X.shape[1] + 1 <= 47."""
+    sum_i (wa*y_i + wb) xa_i xa_i^T  [D, D]), D = X.shape[1] + 1."""
     tot = lr_encode_many([X], [y], mean, sd, wa, wb)[0]
     D = X.shape[1] + 1
     return tot[D, :D], tot[:D, :D]
@@ -1212,21 +1223,27 @@ def _lr_blocks(N: int) -> int:
 
 def lr_encode_many(Xs: list, ys: list, mean, sd, wa: float, wb: float) -> torch.Tensor:
     """``lr_encode`` of several DPs' records with the same standardisation:
-    one encoder launch per DP into one partial slab, then ONE reduction
+    one encoder call per DP into one partial slab, then ONE reduction
     launch (dx_lr_reduce, fixed summation order: a DP's totals are the same
-    bits alone or batched) -> [n, 48, 48] totals (level 1 in row D)."""
+    bits alone or batched) -> [n, P, P] totals with level 2 in [:D, :D] and
+    level 1 in row D (D = features + 1; P = 48 up to 46 features, the
+    16-padded D + 1 beyond; entries outside those are padding)."""
     X0 = Xs[0]
     dev = X0.device
     dx = X0.shape[1]
-    if dx + 1 >= 48:
-        raise ValueError(f"lr_encode supports at most 46 features (got {dx})")
+    if dx < 1:
+        raise ValueError("lr_encode needs at least one feature")
+    D = dx + 1
+    P = _lr_padded(D + 1)
     mean = torch.as_tensor(mean, dtype=torch.float64).to(dev).contiguous()
     sd = torch.as_tensor(sd, dtype=torch.float64).to(dev).contiguous()
     assert mean.numel() == dx and sd.numel() == dx
     nbs = [_lr_blocks(X.shape[0]) for X in Xs]
     nb = max(nbs)
-    alloc = torch.empty if all(b == nb for b in nbs) else torch.zeros  # unused blocks must add nothing
-    partial = alloc((len(Xs), nb, 48, 48), dtype=torch.float64, device=dev)
+    # unused blocks must add nothing; nor may the column tiles past D that a wide launch leaves unwritten
+    full = all(b == nb for b in nbs) and (P == 48 or (D + 15) // 16 == P // 16)
+    alloc = torch.empty if full else torch.zeros
+    partial = alloc((len(Xs), nb, P, P), dtype=torch.float64, device=dev)
     _, s = _ctx(X0)
     keep = []
     for i, (X, y) in enumerate(zip(Xs, ys)):
@@ -1235,12 +1252,13 @@ def lr_encode_many(Xs: list, ys: list, mean, sd, wa: float, wb: float) -> torch.
         y = y.to(device=dev, dtype=torch.float64).contiguous()
         assert y.numel() == N
         keep.append(y)
-        rc = _raw_call("dx_lr_encode", s, _ptr(X), X.stride(0), N, dx, _ptr(mean), _ptr(sd), _ptr(y), float(wa),
-                       float(wb), _ptr(partial[i]), nbs[i])
+        # rows may be strided (a column slice of a wider matrix): the kernel takes the row stride
+        rc = _raw_call("dx_lr_encode", s, ctypes.c_void_p(X.data_ptr()), X.stride(0), N, dx, _ptr(mean), _ptr(sd),
+                       _ptr(y), float(wa), float(wb), _ptr(partial[i]), nbs[i], P)
         if rc != 0:
             raise RuntimeError(f"dx_lr_encode failed rc={rc}")
-    out = torch.empty((len(Xs), 48, 48), dtype=torch.float64, device=dev)
-    rc = _raw_call("dx_lr_reduce", s, _ptr(partial), nb, 48 * 48, len(Xs), _ptr(out))
+    out = torch.empty((len(Xs), P, P), dtype=torch.float64, device=dev)
+    rc = _raw_call("dx_lr_reduce", s, _ptr(partial), nb, P * P, len(Xs), _ptr(out))
     if rc != 0:
         raise RuntimeError(f"dx_lr_reduce failed rc={rc}")
     return out
