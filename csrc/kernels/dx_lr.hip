@@ -31,6 +31,12 @@
 // count beyond that); a tiny second pass (dx_lr_reduce: fixed summation order
 // over the [blocks,P,P] slab, batched over the DPs of a rank) finishes
 // deterministically.
+//
+// Distinct-coefficient layout (query extension Packing = 1): level 2 is
+// symmetric, so only (i, j), i <= j, is sent.  dx_lr_encode_upper launches the
+// same instantiations but not the tile-blocks strictly below the diagonal
+// (unless they hold row D), and dx_lr_reduce_pack does block sum, gather of
+// [level 1, upper triangle] and the rounding to int64 in one launch.
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <cstdio>
@@ -199,7 +205,13 @@ int lr_padded(int D, int level1) {
   return nt <= kTiles ? kD : nt * kTile;
 }
 
-int launch(void *stream_, const LrArgs &a, double *partial, int n_blocks, int P) {
+// upper: the plan of the packed (distinct-coefficient) layout, which reads
+// level 2 only at (i, j), i <= j, and the level-1 row D.  Tile-block (Y, Z) of
+// the 3x3 grid lies strictly below the diagonal when Y > Z; row D sits in the
+// last row tile, hence in the last tile-block row, which is launched whole.
+// Every launched tile-block is the same instantiation over the same record
+// blocks as in the full plan, so what it writes is the same bits.
+int launch(void *stream_, const LrArgs &a, double *partial, int n_blocks, int P, bool upper = false) {
   const int D = a.dx + a.aug;
   if (a.dx <= 0 || n_blocks <= 0 || P != lr_padded(D, a.level1)) return -2;
   if ((a.level1 || !a.w) && !a.y) return -2;
@@ -210,7 +222,15 @@ int launch(void *stream_, const LrArgs &a, double *partial, int n_blocks, int P)
     // live tiles: rows 0..D (with level 1), columns 0..D-1; full 3x3 tile-blocks, then the ragged edges
     const int ntr = P / kTile, ntc = (D + kTile - 1) / kTile;
     const int fa = ntr / kTiles, ra = ntr % kTiles, fb = ntc / kTiles, rb = ntc % kTiles;
-    launch_tiles<kTiles, kTiles>(stream, a, partial, n_blocks, 0, 0, fa, fb, P);
+    if (!upper) {
+      launch_tiles<kTiles, kTiles>(stream, a, partial, n_blocks, 0, 0, fa, fb, P);
+    } else {
+      for (int Y = 0; Y < fa; Y++) {
+        const int z0 = (a.level1 && ra == 0 && Y == fa - 1) ? 0 : Y;  // the tile-block row of row D: whole
+        launch_tiles<kTiles, kTiles>(stream, a, partial, n_blocks, Y * kTiles, z0 * kTiles, 1, fb - z0, P);
+      }
+    }
+    // the ragged right column is at or above the diagonal (fb >= every full Y), the ragged bottom row holds row D
     launch_rows(stream, a, partial, n_blocks, 0, fb * kTiles, fa, 1, P, kTiles, rb);
     launch_rows(stream, a, partial, n_blocks, fa * kTiles, 0, 1, fb, P, ra, kTiles);
     launch_rows(stream, a, partial, n_blocks, fa * kTiles, fb * kTiles, 1, 1, P, ra, rb);
@@ -283,6 +303,86 @@ extern "C" int dx_lr_encode(void *stream, const double *X, int64_t ldx, int64_t 
                             int P) {
   LrArgs a{X, ldx, N, dx, 1, mean, sd, nullptr, y, wa, wb, 1};
   return launch(stream, a, partial, n_blocks, P);
+}
+
+// The upper launch plan of dx_lr_encode (same arguments, same kernels): the
+// tile-blocks strictly below the diagonal that do not hold the level-1 row D
+// are not launched, so their part of the slab is NOT written.  For the packed
+// reducer below, which reads only (i, j), i <= j, and row D.
+extern "C" int dx_lr_encode_upper(void *stream, const double *X, int64_t ldx, int64_t N, int dx, const double *mean,
+                                  const double *sd, const double *y, double wa, double wb, double *partial,
+                                  int n_blocks, int P) {
+  LrArgs a{X, ldx, N, dx, 1, mean, sd, nullptr, y, wa, wb, 1};
+  return launch(stream, a, partial, n_blocks, P, true);
+}
+
+// Block partials -> the packed integer vector a DP encrypts, in one launch:
+// out[i] = [level 1 (row D, columns 0..D-1), level 2 upper triangle row-major
+// (0,0),(0,1),..,(0,D-1),(1,1),..,(D-1,D-1)], entry (a, c), a <= c, at
+// D + a*D - a(a-1)/2 + (c - a).  One thread per (item, packed element);
+// consecutive threads read consecutive columns of a row.  The blocks are
+// summed exactly as lr_reduce_kernel sums them, and the rounding is
+// round_precision's fp64 operations (x = v * precision, floor(|x| + 0.5) with
+// the sign of x: half away from zero, 0 for x == +-0), so a packed value is
+// the same bits as the cartesian path's value at (a, c).
+namespace {
+__global__ void __launch_bounds__(256) lr_reduce_pack_kernel(const double *__restrict__ partial, int64_t nb, int P,
+                                                             int D, int64_t n_items, double precision,
+                                                             int64_t *__restrict__ out, double *__restrict__ fout) {
+  const int64_t n_out = (int64_t)D + (int64_t)D * (D + 1) / 2;
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n_items * n_out) return;
+  const int64_t i = t / n_out, e = t % n_out;
+  int64_t r, c;
+  if (e < D) {
+    r = D;
+    c = e;
+  } else {
+    const int64_t q = e - D;
+    // row a: the largest a with off(a) = a*D - a(a-1)/2 <= q
+    const double m = 2.0 * D + 1.0;
+    int64_t a = (int64_t)((m - sqrt(m * m - 8.0 * (double)q)) * 0.5);
+    a = a < 0 ? 0 : (a > D - 1 ? D - 1 : a);
+    while (a > 0 && a * D - a * (a - 1) / 2 > q) a--;
+    while (a + 1 < D && (a + 1) * D - (a + 1) * a / 2 <= q) a++;
+    r = a;
+    c = a + (q - (a * D - a * (a - 1) / 2));
+  }
+  const int64_t n_el = (int64_t)P * P;
+  const double *p = partial + i * nb * n_el + r * P + c;
+  double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
+  int64_t b = 0;
+  for (; b + 4 <= nb; b += 4) {
+    s0 += p[(b + 0) * n_el];
+    s1 += p[(b + 1) * n_el];
+    s2 += p[(b + 2) * n_el];
+    s3 += p[(b + 3) * n_el];
+  }
+  if (b < nb) s0 += p[b * n_el];
+  if (b + 1 < nb) s1 += p[(b + 1) * n_el];
+  if (b + 2 < nb) s2 += p[(b + 2) * n_el];
+  const double v = (s0 + s1) + (s2 + s3);
+  if (fout) fout[t] = v;
+  const double x = __dmul_rn(v, precision);  // no contraction with the + 0.5 below
+  const int64_t mag = (int64_t)floor(__dadd_rn(fabs(x), 0.5));
+  out[t] = x > 0.0 ? mag : (x < 0.0 ? -mag : 0);
+}
+}  // namespace
+
+// partial: [n_items][nb][P][P]; out: int64 [n_items][D + D(D+1)/2]; fout: the
+// unrounded packed values (same shape, fp64) or null.
+extern "C" int dx_lr_reduce_pack(void *stream, const double *partial, int64_t nb, int P, int D, int64_t n_items,
+                                 double precision, int64_t *out, double *fout) {
+  if (D <= 0 || P <= D || nb <= 0 || n_items <= 0) return -2;  // rows 0..D must lie inside the slab
+  const int64_t n = n_items * ((int64_t)D + (int64_t)D * (D + 1) / 2);
+  hipLaunchKernelGGL(lr_reduce_pack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                     partial, nb, P, D, n_items, precision, out, fout);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) {
+    fprintf(stderr, "[drynx_amd native] lr_reduce_pack: %s\n", hipGetErrorString(e));
+    return -1;
+  }
+  return 0;
 }
 
 // Querier gradient descent for k = 2 (FindMinimumWeights, reference

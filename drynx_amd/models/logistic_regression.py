@@ -30,7 +30,7 @@ import torch
 
 from .. import native as nt
 from ..crypto import elgamal as eg
-from ..query import LogisticRegressionParameters
+from ..query import LogisticRegressionParameters, lr_nbr_outputs
 from ..utils import timers
 from ..utils.log import get_logger
 
@@ -103,8 +103,52 @@ def augment(X: torch.Tensor) -> torch.Tensor:
     return torch.cat([torch.ones((X.shape[0], 1), dtype=X.dtype, device=X.device), X], dim=1)
 
 
-def n_coeffs(d: int, k: int) -> int:
-    return sum((d + 1) ** (j + 1) for j in range(k))
+def n_coeffs(d: int, k: int, packing: int = 0) -> int:
+    """Values a DP sends: cartesian sum_j (d+1)^(j+1), or with distinct packing
+    (1, k <= 2) D + D(D+1)/2 with D = d + 1."""
+    if packing == 0:
+        return sum((d + 1) ** (j + 1) for j in range(k))
+    return lr_nbr_outputs(d, k, packing)
+
+
+# ----------------------------------------------------------------------------- distinct-coefficient packing
+# Query extension (LogisticRegressionParameters.Packing = 1, K <= 2): level 2,
+# the symmetric matrix sum_i w_i xa_i xa_i^T, travels as its row-major upper
+# triangle (0,0),(0,1),..,(0,d),(1,1),..,(d,d).  The values are the cartesian
+# ones at those positions (ComputeAllApproxCoefficients semantics, weight
+# ypart_2), NOT the reference's ComputeDistinctApproxCoefficients, which
+# carries the level-1 sign into level 2 (``distinct_approx_coefficients``).
+def packed_index(i: int, j: int, D: int) -> int:
+    """Position of entry (i, j), i <= j, in the packed level 2."""
+    assert 0 <= i <= j < D
+    return i * D - i * (i - 1) // 2 + (j - i)
+
+
+_triu_memo: dict = {}
+
+
+def _triu_flat(D: int) -> torch.Tensor:
+    """Flat cartesian positions i * D + j of the packed level-2 entries, in packed order."""
+    t = _triu_memo.get(D)
+    if t is None:
+        iu = torch.triu_indices(D, D)  # row-major: (0,0),(0,1),..,(0,D-1),(1,1),..
+        t = _triu_memo[D] = iu[0] * D + iu[1]
+    return t
+
+
+def pack(vals, d: int, k: int):
+    """Cartesian vector [level 1, level 2 (D*D)] -> the distinct layout (a
+    tensor for a tensor, a list otherwise)."""
+    D = d + 1
+    if k == 1:
+        return vals
+    if k != 2:
+        raise ValueError("distinct packing is defined for K <= 2 only")
+    idx = _triu_flat(D)
+    if isinstance(vals, torch.Tensor):
+        return torch.cat([vals[..., :D], vals[..., D:].index_select(-1, idx.to(vals.device))], -1)
+    vals = list(vals)
+    return vals[:D] + [vals[D + e] for e in idx.tolist()]
 
 
 # ----------------------------------------------------------------------------- approximation coefficients
@@ -175,6 +219,11 @@ def encode_coefficients_int_many(Xs: list, ys: list, params: LogisticRegressionP
     d = Xs[0].shape[1] if Xs[0] is not None and Xs[0].dim() == 2 else -1
     if d < 1 or any(X is None or not X.is_cuda or X.dim() != 2 or X.shape[1] != d or len(X) == 0 for X in Xs):
         return None
+    if params.Packing == 1:
+        # distinct layout: the upper launch plan per DP, then one reduce + pack + round launch
+        packed = nt.lr_encode_packed_many([X.to(torch.float64) for X in Xs], ys, params.Means,
+                                          params.StandardDeviations, 0.0, -1.0, params.PrecisionApproxCoefficients)
+        return packed[:, :d + 1] if params.K == 1 else packed
     tot = nt.lr_encode_many([X.to(torch.float64).contiguous() for X in Xs], ys, params.Means,
                             params.StandardDeviations, 0.0, -1.0)
     D = d + 1
@@ -185,6 +234,8 @@ def encode_coefficients_int_many(Xs: list, ys: list, params: LogisticRegressionP
 def encode_coefficients_int(X: torch.Tensor, y: torch.Tensor, params: LogisticRegressionParameters) -> torch.Tensor:
     """The packed int64 vector the DP encrypts (before encryption)."""
     X = X.to(torch.float64)
+    if params.Packing == 1:
+        return _encode_coefficients_int_packed(X, y, params)
     if X.is_cuda and params.K <= 2:
         # one fused pass over the records: standardise + augment + level 1 + level 2 (dx_lr_encode)
         if params.Means and params.StandardDeviations:
@@ -205,12 +256,34 @@ def encode_coefficients_int(X: torch.Tensor, y: torch.Tensor, params: LogisticRe
     return torch.cat([round_precision(lv, params.PrecisionApproxCoefficients) for lv in levels])
 
 
+def _encode_coefficients_int_packed(X: torch.Tensor, y: torch.Tensor, params) -> torch.Tensor:
+    """``encode_coefficients_int`` in the distinct layout (Packing = 1)."""
+    if params.K > 2:
+        raise ValueError("distinct packing is defined for K <= 2 only")
+    d = X.shape[1]
+    if X.is_cuda:
+        if params.Means and params.StandardDeviations:
+            m, s = params.Means, params.StandardDeviations
+        else:
+            m, s = compute_means_sds(X)
+        packed = nt.lr_encode_packed_many([X], [y], m, s, 0.0, -1.0, params.PrecisionApproxCoefficients)[0]
+        return packed[:d + 1] if params.K == 1 else packed
+    # host: the cartesian levels as for Packing = 0, then the upper triangle
+    if params.Means and params.StandardDeviations:
+        Xs = standardise_with(X, params.Means, params.StandardDeviations)
+    else:
+        Xs = standardise(X)
+    levels = approx_coefficients(augment(Xs), y, params.K)
+    cart = torch.cat([round_precision(lv, params.PrecisionApproxCoefficients) for lv in levels])
+    return pack(cart, d, params.K)
+
+
 def encode_logistic_regression(X, y, params: LogisticRegressionParameters, pk: eg.PublicKeyTable,
                                with_proofs: bool = False, ranges=None):
     from ..ops.encoding import _encrypt_with_proofs
 
     d = params.NbrFeatures
-    n = n_coeffs(d, params.K)
+    n = n_coeffs(d, params.K, params.Packing)
     if X is None or len(X) == 0:
         vals = [0] * n
     else:
@@ -221,7 +294,29 @@ def encode_logistic_regression(X, y, params: LogisticRegressionParameters, pk: e
 
 
 # ----------------------------------------------------------------------------- querier: gradient descent
-def unpack(vals, d: int, k: int) -> list:
+def mirror_upper(upper: torch.Tensor, D: int) -> torch.Tensor:
+    """The D(D+1)/2 packed level-2 values -> the flattened symmetric [D, D] matrix."""
+    assert upper.numel() == D * (D + 1) // 2, (upper.numel(), D)
+    iu = torch.triu_indices(D, D)
+    A2 = torch.zeros((D, D), dtype=upper.dtype)
+    A2[iu[0], iu[1]] = upper
+    return (A2 + torch.triu(A2, 1).T).reshape(-1)
+
+
+def unpack(vals, d: int, k: int, packing: int = 0) -> list:
+    """Per-level float64 tensors in the cartesian layout.  ``packing`` 1: the
+    D(D+1)/2 distinct level-2 values are mirrored into the symmetric [D, D]
+    matrix (on the host), so the descent below is the same for both layouts."""
+    if packing == 1:
+        if k > 2:
+            raise ValueError("distinct packing is defined for K <= 2 only")
+        D = d + 1
+        out = [torch.tensor(vals[:D], dtype=torch.float64)]
+        if k == 2:
+            out.append(mirror_upper(torch.tensor(vals[D: D + D * (D + 1) // 2], dtype=torch.float64), D))
+        return out
+    if packing != 0:
+        raise ValueError(f"unknown packing {packing}")
     out, off = [], 0
     for j in range(k):
         m = (d + 1) ** (j + 1)
@@ -310,14 +405,20 @@ def _find_minimum_weights_k2(approx, initial_weights, N, lam, step, max_iter, ti
 
 
 def find_minimum_weights_with_encryption(encrypted: list, secret: int, initial_weights, N: int, lam: float,
-                                         step: float, max_iter: int, precision: float):
+                                         step: float, max_iter: int, precision: float, packing: int = 0):
     """FindMinimumWeightsWithEncryption (:746-766): the client decrypts the
     encrypted approximation coefficients (one CipherVector per level, with
     negatives), rescales them by ``precision`` and runs FindMinimumWeights.
-    -> (weights, approx coefficients as lists of floats)."""
+    ``packing`` 1: level 2 arrives as its D(D+1)/2 distinct values and is
+    mirrored first.  -> (weights, approx coefficients as lists of floats,
+    cartesian layout)."""
     approx = []
-    for cv in encrypted:
+    for lvl, cv in enumerate(encrypted):
         vals = eg.decrypt_auto(secret, cv).cpu().to(torch.float64)
+        if packing == 1 and lvl == 1:
+            vals = mirror_upper(vals, approx[0].numel())
+        elif packing not in (0, 1) or (packing == 1 and lvl > 1):
+            raise ValueError(f"no packing {packing} for level {lvl + 1}")
         approx.append(vals / precision)
     w = find_minimum_weights(approx, initial_weights, N, lam, step, max_iter)
     return w, [a.tolist() for a in approx]
@@ -325,7 +426,8 @@ def find_minimum_weights_with_encryption(encrypted: list, secret: int, initial_w
 
 def decode_logistic_regression_values(vals, params: LogisticRegressionParameters) -> list:
     with timers.timed("GradientDescent", sync=False):
-        approx = [a / params.PrecisionApproxCoefficients for a in unpack(vals, params.NbrFeatures, params.K)]
+        approx = [a / params.PrecisionApproxCoefficients
+                  for a in unpack(vals, params.NbrFeatures, params.K, params.Packing)]
         init = params.InitialWeights or [0.0] * (params.NbrFeatures + 1)
         return find_minimum_weights(approx, init, params.NbrRecords, params.Lambda, params.Step, params.MaxIterations)
 

@@ -101,6 +101,8 @@ _SIGS = {
     "dx_hash_to_g1": [_I, _P, _P, _P, _L, _P, _L],
     "dx_lr_encode": [_P, _P, _L, _L, _I, _P, _P, _P, ctypes.c_double, ctypes.c_double, _P, _I, _I],
     "dx_lr_reduce": [_P, _P, _L, _L, _L, _P],
+    "dx_lr_encode_upper": [_P, _P, _L, _L, _I, _P, _P, _P, ctypes.c_double, ctypes.c_double, _P, _I, _I],
+    "dx_lr_reduce_pack": [_P, _P, _L, _I, _I, _L, ctypes.c_double, _P, _P],
     "dx_g1_mul_glv256": [_P, _P, _P, _P, _P, _L, _I, _I, _I],
     "dx_glv_split": [_I, _P, _P, _P, _L],
     "dx_gt_t2_compress": [_I, _P, _P, _P, _P, _L],
@@ -1221,13 +1223,11 @@ def _lr_blocks(N: int) -> int:
     return int(max(1, min(1024, (steps + 15) // 16)))
 
 
-def lr_encode_many(Xs: list, ys: list, mean, sd, wa: float, wb: float) -> torch.Tensor:
-    """``lr_encode`` of several DPs' records with the same standardisation:
-    one encoder call per DP into one partial slab, then ONE reduction
-    launch (dx_lr_reduce, fixed summation order: a DP's totals are the same
-    bits alone or batched) -> [n, P, P] totals with level 2 in [:D, :D] and
-    level 1 in row D (D = features + 1; P = 48 up to 46 features, the
-    16-padded D + 1 beyond; entries outside those are padding)."""
+def _lr_launch_many(Xs: list, ys: list, mean, sd, wa: float, wb: float, upper: bool):
+    """One encoder call per DP into one [n, nb, P, P] partial slab (nb = the
+    longest DP's record blocks) -> (slab, D).  ``upper``: the packed layout's
+    launch plan (dx_lr_encode_upper), which leaves the tile-blocks strictly
+    below the diagonal unwritten."""
     X0 = Xs[0]
     dev = X0.device
     dx = X0.shape[1]
@@ -1240,12 +1240,21 @@ def lr_encode_many(Xs: list, ys: list, mean, sd, wa: float, wb: float) -> torch.
     assert mean.numel() == dx and sd.numel() == dx
     nbs = [_lr_blocks(X.shape[0]) for X in Xs]
     nb = max(nbs)
-    # unused blocks must add nothing; nor may the column tiles past D that a wide launch leaves unwritten
-    full = all(b == nb for b in nbs) and (P == 48 or (D + 15) // 16 == P // 16)
+    # Invariant: the slab is torch.empty only when every record block of every
+    # DP is written AND every element the reducer will read is written;
+    # otherwise it is zero-filled, so that what is read but unwritten adds
+    # nothing.  A shorter DP's trailing blocks are never written.  The full
+    # reducer reads all of [P, P], of which a wide launch leaves the column
+    # tiles past D unwritten.  The packed reducer reads only (i, j), i <= j < D,
+    # and row D, all of which the upper plan writes: what that plan skips
+    # (below the diagonal) and the padding columns are never read, so they may
+    # stay uninitialised.
+    full = all(b == nb for b in nbs) and (upper or P == 48 or (D + 15) // 16 == P // 16)
     alloc = torch.empty if full else torch.zeros
     partial = alloc((len(Xs), nb, P, P), dtype=torch.float64, device=dev)
     _, s = _ctx(X0)
     keep = []
+    name = "dx_lr_encode_upper" if upper else "dx_lr_encode"
     for i, (X, y) in enumerate(zip(Xs, ys)):
         assert X.is_cuda and X.dtype == torch.float64 and X.dim() == 2 and X.stride(1) == 1 and X.shape[1] == dx
         N = X.shape[0]
@@ -1253,15 +1262,75 @@ def lr_encode_many(Xs: list, ys: list, mean, sd, wa: float, wb: float) -> torch.
         assert y.numel() == N
         keep.append(y)
         # rows may be strided (a column slice of a wider matrix): the kernel takes the row stride
-        rc = _raw_call("dx_lr_encode", s, ctypes.c_void_p(X.data_ptr()), X.stride(0), N, dx, _ptr(mean), _ptr(sd),
+        rc = _raw_call(name, s, ctypes.c_void_p(X.data_ptr()), X.stride(0), N, dx, _ptr(mean), _ptr(sd),
                        _ptr(y), float(wa), float(wb), _ptr(partial[i]), nbs[i], P)
         if rc != 0:
-            raise RuntimeError(f"dx_lr_encode failed rc={rc}")
-    out = torch.empty((len(Xs), P, P), dtype=torch.float64, device=dev)
-    rc = _raw_call("dx_lr_reduce", s, _ptr(partial), nb, P * P, len(Xs), _ptr(out))
+            raise RuntimeError(f"{name} failed rc={rc}")
+    return partial, D
+
+
+def lr_reduce(partial: torch.Tensor) -> torch.Tensor:
+    """Block partials [n, nb, P, P] -> totals [n, P, P] (dx_lr_reduce: block b
+    into accumulator b % 4, combined as (s0 + s1) + (s2 + s3))."""
+    assert partial.is_cuda and partial.dtype == torch.float64 and partial.dim() == 4 and partial.is_contiguous()
+    n, nb, P, P2 = partial.shape
+    assert P == P2 and n >= 1 and nb >= 1
+    out = torch.empty((n, P, P), dtype=torch.float64, device=partial.device)
+    _, s = _ctx(partial)
+    rc = _raw_call("dx_lr_reduce", s, _ptr(partial), nb, P * P, n, _ptr(out))
     if rc != 0:
         raise RuntimeError(f"dx_lr_reduce failed rc={rc}")
     return out
+
+
+def lr_encode_many(Xs: list, ys: list, mean, sd, wa: float, wb: float) -> torch.Tensor:
+    """``lr_encode`` of several DPs' records with the same standardisation:
+    one encoder call per DP into one partial slab, then ONE reduction
+    launch (dx_lr_reduce, fixed summation order: a DP's totals are the same
+    bits alone or batched) -> [n, P, P] totals with level 2 in [:D, :D] and
+    level 1 in row D (D = features + 1; P = 48 up to 46 features, the
+    16-padded D + 1 beyond; entries outside those are padding)."""
+    partial, _ = _lr_launch_many(Xs, ys, mean, sd, wa, wb, False)
+    return lr_reduce(partial)
+
+
+def lr_packed_len(D: int) -> int:
+    """Length of the distinct-coefficient vector: level 1 (D) + the upper triangle of level 2."""
+    return D + D * (D + 1) // 2
+
+
+def lr_reduce_pack(partial: torch.Tensor, D: int, precision: float, floats: bool = False):
+    """Block partials [n, nb, P, P] (or [nb, P, P]: one item) -> the packed
+    int64 vectors [n, D + D(D+1)/2] in ONE launch (dx_lr_reduce_pack): level 1
+    from row D, then level 2's upper triangle row-major, summed over the
+    blocks in dx_lr_reduce's order, times ``precision``, rounded half away from
+    zero.  Reads only (i, j), i <= j < D, and row D of each block.
+    ``floats``: also return the unrounded packed fp64 values."""
+    if partial.dim() == 3:
+        partial = partial[None]
+    assert partial.is_cuda and partial.dtype == torch.float64 and partial.dim() == 4 and partial.is_contiguous()
+    n, nb, P, P2 = partial.shape
+    D = int(D)
+    if not (P == P2 and 1 <= D < P and n >= 1 and nb >= 1):
+        raise ValueError(f"lr_reduce_pack: slab {tuple(partial.shape)} does not hold rows 0..{D}")
+    dev = partial.device
+    out = torch.empty((n, lr_packed_len(D)), dtype=torch.int64, device=dev)
+    fout = torch.empty((n, lr_packed_len(D)), dtype=torch.float64, device=dev) if floats else None
+    _, s = _ctx(partial)
+    rc = _raw_call("dx_lr_reduce_pack", s, _ptr(partial), nb, P, D, n, float(precision), _ptr(out), _ptr(fout))
+    if rc != 0:
+        raise RuntimeError(f"dx_lr_reduce_pack failed rc={rc}")
+    return (out, fout) if floats else out
+
+
+def lr_encode_packed_many(Xs: list, ys: list, mean, sd, wa: float, wb: float, precision: float, floats: bool = False):
+    """The distinct-coefficient integer vectors of several DPs' records ->
+    int64 [n, D + D(D+1)/2] (``floats``: and the unrounded fp64 values): per DP
+    the encoder's upper launch plan, then ONE reduce + pack + round launch for
+    the batch.  Rows may be strided, any d >= 1, DPs of unequal length.  Entry
+    (i, j), i <= j, is the same bits as ``lr_encode_many``'s value there."""
+    partial, D = _lr_launch_many(Xs, ys, mean, sd, wa, wb, True)
+    return lr_reduce_pack(partial, D, precision, floats)
 
 
 # ----------------------------------------------------------------------------- range proofs (K15/K16)

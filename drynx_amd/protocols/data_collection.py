@@ -40,7 +40,7 @@ def expected_n_out(sq) -> int | None:
     cf = max(1, q.CuttingFactor or 1)
     if op.NameOp == "logistic regression":
         p = op.LRParameters
-        return None if p is None else lr_nbr_outputs(p.NbrFeatures, p.K) * cf
+        return None if p is None else lr_nbr_outputs(p.NbrFeatures, p.K, p.Packing) * cf
     return (op.NbrOutput // cf) * cf if op.NbrOutput > 0 else None
 
 
@@ -187,7 +187,8 @@ def _lr_values(ctx, sq, dps: list, device) -> torch.Tensor:
     out = []
     for X, y in data:
         if X is None or len(X) == 0:
-            out.append(torch.zeros(n_coeffs(params.NbrFeatures, params.K), dtype=torch.int64, device=device))
+            out.append(torch.zeros(n_coeffs(params.NbrFeatures, params.K, params.Packing), dtype=torch.int64,
+                                   device=device))
         else:
             out.append(encode_coefficients_int(torch.as_tensor(X, device=device), torch.as_tensor(y, device=device),
                                                params).to(device))

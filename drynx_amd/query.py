@@ -130,6 +130,10 @@ class LogisticRegressionParameters:
     InitialWeights: list = field(default_factory=list)
     K: int = 2
     PrecisionApproxCoefficients: float = 1.0
+    # extension: layout of the level-2 coefficients.  0 = the reference's
+    # cartesian (d+1)^2 values; 1 = distinct: only the upper triangle (i <= j)
+    # of the symmetric level-2 matrix, row-major, D(D+1)/2 values (K <= 2).
+    Packing: int = 0
 
 
 @dataclass
@@ -340,6 +344,12 @@ def check_parameters(sq: SurveyQuery, diffp: bool) -> bool:
     else:
         if (d.Limit == 0.0 and d.Quanta == 0.0) or d.Scale == 0.0 or d.NoiseListSize == 0 or d.LapScale == 0.0:
             msg.append("diffP but parameters are 0")
+    if q.Operation.NameOp == "logistic regression" and q.Operation.LRParameters is not None:
+        lrp = q.Operation.LRParameters
+        if lrp.Packing not in (0, 1):
+            msg.append("logistic regression packing is neither 0 (cartesian) nor 1 (distinct)")
+        elif lrp.Packing == 1 and lrp.K > 2:
+            msg.append("distinct packing is defined for K <= 2 only")
     if q.Operation.QueryMin != q.DPDataGen.GenerateDataMin or q.Operation.QueryMax != q.DPDataGen.GenerateDataMax:
         msg.append("min or max are inconsistent at DP and operations")
     for m in msg:
@@ -390,9 +400,16 @@ def choose_operation(name: str, query_min: int, query_max: int, d: int, cutting_
     return op
 
 
-def lr_nbr_outputs(d: int, k: int) -> int:
-    """getTotalNumberApproxCoefficients (logistic_regression.go:306): sum_j (d+1)^(j+1)."""
-    return sum((d + 1) ** (j + 1) for j in range(k))
+def lr_nbr_outputs(d: int, k: int, packing: int = 0) -> int:
+    """getTotalNumberApproxCoefficients (logistic_regression.go:306): sum_j (d+1)^(j+1).
+    ``packing`` 1 (extension, k <= 2): level 2 is sent as the D(D+1)/2 distinct
+    entries (i <= j) of the symmetric matrix, D = d + 1."""
+    if packing == 0:
+        return sum((d + 1) ** (j + 1) for j in range(k))
+    if packing != 1 or k > 2:
+        raise ValueError(f"no packing {packing} for k = {k}")
+    D = d + 1
+    return D if k == 1 else D + D * (D + 1) // 2
 
 
 def new_survey_id() -> str:

@@ -40,7 +40,9 @@ ROSTER = (("ID", "bytes"), ("List", ("rep", ("msg", SERVER_IDENTITY))), ("Aggreg
 LR_PARAMETERS = (("DatasetName", "string"), ("FilePath", "string"), ("NbrRecords", "sint"), ("NbrFeatures", "sint"),
                  ("Means", ("rep", "double")), ("StandardDeviations", ("rep", "double")), ("Lambda", "double"),
                  ("Step", "double"), ("MaxIterations", "sint"), ("InitialWeights", ("rep", "double")),
-                 ("K", "sint"), ("PrecisionApproxCoefficients", "double"))
+                 ("K", "sint"), ("PrecisionApproxCoefficients", "double"),
+                 # drynx_amd extension (after the reference fields): 1 = distinct-coefficient packing of level 2
+                 ("Packing", "sint"))
 OPERATION = (("NameOp", "string"), ("NbrInput", "sint"), ("NbrOutput", "sint"), ("QueryMin", "sint"),
              ("QueryMax", "sint"), ("LRParameters", ("msg", LR_PARAMETERS)))
 QUERY_DIFFP = (("LapMean", "double"), ("LapScale", "double"), ("NoiseListSize", "sint"), ("Quanta", "double"),
