@@ -1,4 +1,4 @@
-"""Lifetime of cached device-resident bucket plans (native._device_layout).
+"""Lifetime of cached device-resident bucket plans (native.msm._device_layout).
 
 Round 5 captured the pool verifier's passes in HIP graphs and saw replays
 fault (profiles/r6/graph_fault.md): the plan cache evicts layouts (32 shapes)
@@ -10,6 +10,7 @@ import pytest
 import torch
 
 from drynx_amd import native as nt
+from drynx_amd.native import msm
 
 
 def _shape(i):
@@ -18,21 +19,21 @@ def _shape(i):
 
 def test_capture_keep_collects_layouts():
     with nt.capture_keep() as ck:
-        a = nt._device_layout(_shape(0), 8, 8, 32, "cpu")
-        b = nt._device_layout(_shape(1), 8, 8, 32, "cpu")
+        a = msm._device_layout(_shape(0), 8, 8, 32, "cpu")
+        b = msm._device_layout(_shape(1), 8, 8, 32, "cpu")
     assert ck.items[0] is a and ck.items[1] is b
-    nt._device_layout(_shape(2), 8, 8, 32, "cpu")
+    msm._device_layout(_shape(2), 8, 8, 32, "cpu")
     assert len(ck.items) == 2  # collection ends with the block
 
 
 def test_eviction_keeps_captured_layouts_alive(monkeypatch):
-    monkeypatch.setattr(nt, "_PLAN_LIMIT", 2)
+    monkeypatch.setattr(msm, "_PLAN_LIMIT", 2)
     with nt.capture_keep() as ck:
-        held = nt._device_layout(_shape(10), 8, 8, 32, "cpu")
+        held = msm._device_layout(_shape(10), 8, 8, 32, "cpu")
     for i in range(11, 20):  # evicts shape 10 from the cache
-        nt._device_layout(_shape(i), 8, 8, 32, "cpu")
+        msm._device_layout(_shape(i), 8, 8, 32, "cpu")
     key = (_shape(10), 8, 8, 32, "cpu")
-    assert key not in nt._DPLANS and ck.items[0] is held
+    assert key not in msm._DPLANS and ck.items[0] is held
     assert held["lane_bucket"].numel() == held["n_lanes"]  # still a live tensor the graph can read
 
 
@@ -40,9 +41,9 @@ def test_eviction_keeps_captured_layouts_alive(monkeypatch):
 def test_layout_records_every_user_stream(gpu_device):
     s1, s2 = torch.cuda.Stream(gpu_device), torch.cuda.Stream(gpu_device)
     with torch.cuda.stream(s1):
-        lay = nt._device_layout(_shape(40), 8, 8, 32, gpu_device)
+        lay = msm._device_layout(_shape(40), 8, 8, 32, gpu_device)
     with torch.cuda.stream(s2):
-        again = nt._device_layout(_shape(40), 8, 8, 32, gpu_device)
+        again = msm._device_layout(_shape(40), 8, 8, 32, gpu_device)
     assert again is lay and {s1.stream_id, s2.stream_id} <= lay["_streams"]
 
 

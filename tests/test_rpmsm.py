@@ -195,6 +195,9 @@ def test_multi_exp_and_g1_msm_device_plans(device, wc):
     for i in range(n):
         want1 = want1 * pw(a_pts[i], e40[i])
     assert bn.gt_from_tensor(got.cpu()) == [want0, want1]
+    # the counted plan on the same input: rows 2n .. 3n-1 read a[i % n] = a[(i - 2n) % n]
+    got = nt.multi_exp_grouped_finish(nt.multi_exp_grouped(a, k, grp, 2, *wc))
+    assert bn.gt_from_tensor(got.cpu()) == [want0, want1]
     # an exponent wider than group 0's declared 32 bits
     k2 = k.clone()
     k2[0, 1] = 1
