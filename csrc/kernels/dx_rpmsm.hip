@@ -21,6 +21,19 @@
 //     segmented bucket sums, bucket weights d B_d, per-window sums and a
 //     Horner step per verifier that writes R straight into the Miller-loop
 //     input list: no host round trip between the MSM and the pairing fold).
+// When the proofs of several DPs answer the same columns, Y_pi = c_p y_k with
+// the same key y_k = y_(col(p), i) for every proof p of a key group k, and the
+// U side is regrouped once more:
+//     prod_(p in k) e(-c_p y_k, U_pi) = e(-y_k, U'_k),   U'_k = sum_(p in k) c_p U_pi,
+// i.e. (number of distinct keys) + 1 Miller loops per verifier instead of
+// n*S + 1, and no c_p y products:
+//   * c_p = k1 + s k2 lambda with 128-bit halves (glv_split.h; the same
+//     lambda), so U'_k is the joint-window ladder again, over 64 windows and
+//     the signed table of (U, +-[lambda] U) per U row (joint_table_one with
+//     sgn), the doublings shared by the members of a group (u_group_kernel);
+//   * every U_pi is still computed and tested for G2 membership -- [lambda]
+//     acts as (TWX2 x, y) on G2 only -- and a failing batch gets its
+//     per-request products from the per-item fold over the same U rows.
 // Soundness: the check is the same equation (bilinearity on G2 x G1); every
 // V_it is on the twist (decode check), the combined points are in G2 by
 // construction when the V_it are, and a failed batch falls back to the
@@ -53,7 +66,9 @@ constexpr int kWG = 64;
 // per-entry arrays in the thread's frame (the previous Jacobian version kept
 // 15 Z values and prefix products there: 3,360 B of scratch per lane,
 // profiles/r5/kernel_resources.txt) and ~1/3 of its field products.
-DX_HD void joint_table_one(const uint32_t *V_aff, uint32_t *T_aff, int64_t it) {
+// sgn (optional, one word per V): nonzero builds the table over (V, -[lambda] V)
+// instead -- the second axis of a GLV-split scalar whose k2 is negative.
+DX_HD void joint_table_one(const uint32_t *V_aff, const int32_t *sgn, uint32_t *T_aff, int64_t it) {
   G2A *T = reinterpret_cast<G2A *>(T_aff) + it * kT;
   const G2A v = at<G2A>(V_aff, it);
   if (v.is_inf()) {
@@ -72,12 +87,14 @@ DX_HD void joint_table_one(const uint32_t *V_aff, uint32_t *T_aff, int64_t it) {
     T[0] = v;                                 // (1, 0)
     T[1] = A2;                                // (2, 0)
     T[2] = A3;                                // (3, 0)
-    T[3] = G2A{mul_fp(v.x, tw), v.y};         // (0, 1)
-    T[7] = G2A{mul_fp(A2.x, tw), A2.y};       // (0, 2)
-    T[11] = G2A{mul_fp(A3.x, tw), A3.y};      // (0, 3)
+    const bool ng = sgn && sgn[it];
+    T[3] = G2A{mul_fp(v.x, tw), ng ? neg(v.y) : v.y};         // (0, 1)
+    T[7] = G2A{mul_fp(A2.x, tw), ng ? neg(A2.y) : A2.y};      // (0, 2)
+    T[11] = G2A{mul_fp(A3.x, tw), ng ? neg(A3.y) : A3.y};     // (0, 3)
   }
   // mixed entries e = da + 4 db - 1, da, db in 1..3: forward prefix products
-  // of d_e = x(db [lambda] V) - x(da V) (nonzero: da V != +-db [lambda] V)
+  // of d_e = x(db [lambda] V) - x(da V) (nonzero: da V != +-db [lambda] V;
+  // a point and its negative share x, so either sign of the second axis)
   Fp2 acc = Fp2::one();
   for (int db = 1; db < 4; db++) {
     for (int da = 1; da < 4; da++) {
@@ -157,6 +174,39 @@ DX_HD void u_joint_reduce_one(const uint32_t *P_jac, uint32_t *U_aff, int64_t n_
   G2J acc = at<G2J>(P_jac, vq * sp);
   for (int p = 1; p < sp; p++) acc = jadd(acc, at<G2J>(P_jac, vq * sp + p));
   at<G2A>(U_aff, pos ? pos[vq] : v * pad + q) = to_affine(acc);
+}
+
+// Key-group combination (the verifier's second regrouping: every proof of a
+// group pairs with the same G1 key, so prod_p e(-c_p y, U_p) = e(-y, sum_p c_p U_p)).
+// Part `part` of (verifier v, group g): members k = part, part + sp, ... of
+// idx[start[g] .. start[g] + len[g]); member q is U row v * nq + q (its signed
+// joint table: T rows (v nq + q) 15 ..) with the GLV-split challenge of proof
+// q / S (split [n, 9]: k1, |k2|, sign; the sign is in the table).  The joint
+// 2-bit-window ladder of u_joint_one over the 64 windows of 128-bit halves;
+// the doublings are shared by the part's members.
+DX_HD G2J u_group_part(const uint32_t *T_aff, const uint32_t *split, const int32_t *idx, const int64_t *start,
+                       const int32_t *len, int64_t n_groups, int64_t nq, int S, int sp, int64_t t) {
+  const int part = (int)(t % sp);
+  const int64_t vg = t / sp;
+  const int64_t v = vg / n_groups, g = vg % n_groups;
+  const int64_t b = start[g];
+  const int n = len[g];
+  const G2A *T = reinterpret_cast<const G2A *>(T_aff) + v * nq * kT;
+  G2J acc = G2J::inf();
+  for (int win = 63; win >= 0; win--) {
+    if (win != 63) {
+      acc = jdbl(acc);
+      acc = jdbl(acc);
+    }
+    const int li = win >> 4, sh = 2 * (win & 15);
+    for (int k = part; k < n; k += sp) {
+      const int64_t q = idx[b + k];
+      const uint32_t *c = split + 9 * (q / S);
+      const uint32_t e = ((c[li] >> sh) & 3u) + 4u * ((c[4 + li] >> sh) & 3u);
+      if (e) acc = jadd_mixed(acc, T[q * kT + e - 1]);
+    }
+  }
+  return acc;
 }
 
 DX_HD void slice_sum_one(const uint32_t *src, const int32_t *idx, const int64_t *start, const int32_t *len,
@@ -259,9 +309,10 @@ __global__ void __launch_bounds__(256) msm_keys_kernel(const uint32_t *k, const 
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i < n * W) msm_keys_one(k, grp, gstride, c, W, keys, items, i);
 }
-__global__ void __launch_bounds__(kWG) DX_OCC joint_table_kernel(const uint32_t *V, uint32_t *T, int64_t m) {
+__global__ void __launch_bounds__(kWG) DX_OCC joint_table_kernel(const uint32_t *V, const int32_t *sgn, uint32_t *T,
+                                                                int64_t m) {
   DX_TID();
-  if (i < m) joint_table_one(V, T, i);
+  if (i < m) joint_table_one(V, sgn, T, i);
 }
 __global__ void __launch_bounds__(kWG) DX_OCC u_joint_kernel(const uint32_t *T, const uint32_t *ab, uint32_t *U,
                                                             int64_t n_groups, int L, int64_t pad, const int64_t *pos,
@@ -327,6 +378,33 @@ __global__ void __launch_bounds__(kWG) DX_OCC u_joint_fused_kernel(const uint32_
     at<G2A>(U, pos ? pos[vq] : v * pad + q) = to_affine(acc);
   }
 }
+// Key-group combinations, sp lanes per (v, g) (sp | 64; sp = 1: one lane
+// each), reduced through LDS as in u_joint_fused_kernel: a group of mu
+// members is a chain of 126 doublings + ~60 mu additions, and a query has
+// only ~19k (v, g) -- one lane each would leave most SIMDs empty.
+__global__ void __launch_bounds__(kWG) DX_OCC u_group_kernel(const uint32_t *T, const uint32_t *split,
+                                                            const int32_t *idx, const int64_t *start,
+                                                            const int32_t *len, uint32_t *U, int64_t n_groups,
+                                                            int64_t nq, int S, int sp, int64_t pad,
+                                                            const int64_t *pos, int64_t n) {
+  __shared__ G2J red[kWG];
+  DX_TID();
+  const bool live = i < n * sp;
+  G2J acc = G2J::inf();
+  if (live) acc = u_group_part(T, split, idx, start, len, n_groups, nq, S, sp, i);
+  const int part = (int)(threadIdx.x % sp);
+  for (int st = 1; st < sp; st <<= 1) {
+    if (part % (2 * st) == st) red[threadIdx.x] = acc;
+    __syncthreads();
+    if (part % (2 * st) == 0) acc = jadd(acc, red[threadIdx.x + st]);
+    __syncthreads();
+  }
+  if (live && part == 0) {
+    const int64_t vg = i / sp;
+    const int64_t v = vg / n_groups, g = vg % n_groups;
+    at<G2A>(U, pos ? pos[vg] : v * pad + g) = to_affine(acc);
+  }
+}
 __global__ void __launch_bounds__(kWG) DX_OCC slice_sum_kernel(const uint32_t *src, const int32_t *idx,
                                                               const int64_t *start, const int32_t *len,
                                                               uint32_t *out, int src_aff, int64_t idx_mod,
@@ -370,14 +448,20 @@ int dx_msm_keys(int on_gpu, void *stream, const uint32_t *k, const int32_t *grp,
   return check_hip(hipGetLastError(), "msm_keys");
 }
 
-int dx_g2_joint_table(int on_gpu, void *stream, const uint32_t *V_aff, uint32_t *T_aff, int64_t m) {
+// sgn: nullptr, or one word per V (nonzero: the table of (V, -[lambda] V))
+int dx_g2_joint_table_signed(int on_gpu, void *stream, const uint32_t *V_aff, const int32_t *sgn, uint32_t *T_aff,
+                             int64_t m) {
   if (m <= 0) return 0;
   if (!on_gpu) {
-    host_for_each(m, [=](int64_t it) { joint_table_one(V_aff, T_aff, it); });
+    host_for_each(m, [=](int64_t it) { joint_table_one(V_aff, sgn, T_aff, it); });
     return 0;
   }
-  hipLaunchKernelGGL(joint_table_kernel, grid_of(m), dim3(kWG), 0, (hipStream_t)stream, V_aff, T_aff, m);
+  hipLaunchKernelGGL(joint_table_kernel, grid_of(m), dim3(kWG), 0, (hipStream_t)stream, V_aff, sgn, T_aff, m);
   return check_hip(hipGetLastError(), "g2_joint_table");
+}
+
+int dx_g2_joint_table(int on_gpu, void *stream, const uint32_t *V_aff, uint32_t *T_aff, int64_t m) {
+  return dx_g2_joint_table_signed(on_gpu, stream, V_aff, nullptr, T_aff, m);
 }
 
 // U[v*pad + q] = affine(sum_{j<L} (a + b lambda)_{v, q*L+j} V_{q*L+j}) for
@@ -415,6 +499,29 @@ int dx_rp_u_joint_split(int on_gpu, void *stream, const uint32_t *T_aff, const u
   hipLaunchKernelGGL(u_joint_reduce_kernel, grid_of(n), dim3(kWG), 0, (hipStream_t)stream, tmp, U_aff, n_groups, sp,
                      pad, pos, n);
   return check_hip(hipGetLastError(), "rp_u_joint_split");
+}
+
+// U[v*pad + g] (or row pos[v*n_groups + g]) = affine(sum_k (k1 + s k2 lambda)_(q_k / S) Uin_(v nq + q_k)),
+// q_k = idx[start[g] + k], k < len[g], for v < G, g < n_groups.  T: the signed
+// joint table of the G * nq rows Uin (sign of row v nq + q: split[9 (q / S) + 8]);
+// split [n, 9]: dx_glv_split of the proofs' challenges.  sp lanes per (v, g)
+// (sp | 64); tmp: G * n_groups * sp Jacobian rows (host path only).
+int dx_rp_u_group(int on_gpu, void *stream, const uint32_t *T_aff, const uint32_t *split, const int32_t *idx,
+                  const int64_t *start, const int32_t *len, uint32_t *U_aff, int64_t n_groups, int G, int64_t nq,
+                  int S, int sp, int64_t pad, const int64_t *pos, uint32_t *tmp) {
+  const int64_t n = (int64_t)G * n_groups;
+  if (n <= 0) return 0;
+  if (sp < 1 || kWG % sp != 0) return 1;
+  if (!on_gpu) {
+    host_for_each(n * sp, [=](int64_t t) {
+      at<G2J>(tmp, t) = u_group_part(T_aff, split, idx, start, len, n_groups, nq, S, sp, t);
+    });
+    host_for_each(n, [=](int64_t t) { u_joint_reduce_one(tmp, U_aff, n_groups, sp, pad, pos, t); });
+    return 0;
+  }
+  hipLaunchKernelGGL(u_group_kernel, grid_of(n * sp), dim3(kWG), 0, (hipStream_t)stream, T_aff, split, idx, start,
+                     len, U_aff, n_groups, nq, S, sp, pad, pos, n);
+  return check_hip(hipGetLastError(), "rp_u_group");
 }
 
 // out[s] = sum_{k < len[s]} src[e_k], e_k = idx[start[s] + k] (mod idx_mod when

@@ -148,6 +148,8 @@ _SIGS = {
     "dx_gt_gls6_pow": [_I, _P, _P, _P, _P, _P, _L],
     "dx_rp_prove_a_gls6": [_I, _P, _P, _P, _P, _P, _P, _P, _L, _I, _I],
     "dx_g2_joint_table": [_I, _P, _P, _P, _L],
+    "dx_g2_joint_table_signed": [_I, _P, _P, _P, _P, _L],
+    "dx_rp_u_group": [_I, _P, _P, _P, _P, _P, _P, _P, _L, _I, _L, _I, _I, _L, _P, _P],
     "dx_rp_u_joint": [_I, _P, _P, _P, _P, _L, _I, _I, _L, _P],
     "dx_g2_slice_sum": [_I, _P, _P, _P, _P, _P, _P, _L, _I, _L],
     "dx_g2_horner": [_I, _P, _P, _P, _I, _I, _I, _L, _L],
@@ -1556,13 +1558,20 @@ def rp_fold_coeffs(V_aff: torch.Tensor) -> torch.Tensor:
 G2_JOINT_ENTRIES = 15
 
 
-def g2_joint_table(V_aff: torch.Tensor) -> torch.Tensor:
+def g2_joint_table(V_aff: torch.Tensor, sign: torch.Tensor | None = None) -> torch.Tensor:
     """Per V: the 15 affine points da V + db [lambda] V ((da, db) in [0, 3]^2,
-    not both 0) -> [m * 15, 32]; the U-combination kernel's window table."""
+    not both 0) -> [m * 15, 32]; the U-combination kernel's window table.
+    ``sign`` (int32 [m]): where nonzero the second axis is -[lambda] V (the
+    table of a GLV-split scalar k1 - |k2| lambda)."""
     m = _rows(V_aff, 32)
     out = torch.empty((m * G2_JOINT_ENTRIES, 32), dtype=torch.int32, device=V_aff.device)
-    g, s = _ctx(V_aff)
-    _call("dx_g2_joint_table", g, s, _ptr(V_aff.contiguous()), _ptr(out), m)
+    if sign is None:
+        g, s = _ctx(V_aff)
+        _call("dx_g2_joint_table", g, s, _ptr(V_aff.contiguous()), _ptr(out), m)
+        return out
+    assert sign.dtype == torch.int32 and sign.numel() == m
+    g, s = _ctx(V_aff, sign)
+    _call("dx_g2_joint_table_signed", g, s, _ptr(V_aff.contiguous()), _ptr(sign.contiguous()), _ptr(out), m)
     return out
 
 
@@ -1589,6 +1598,53 @@ def rp_u_joint(table: torch.Tensor, ab: torch.Tensor, n_groups: int, G: int, L: 
               _ptr(tmp), _ptr(pos))
         return out
     _call("dx_rp_u_joint", g, s, _ptr(table), _ptr(ab.contiguous()), _ptr(out), n_groups, G, L, pad, _ptr(pos))
+    return out
+
+
+def rp_u_group_lanes(n: int, on_gpu: bool) -> int:
+    """Lanes per key-group combination: the (VN, group) pairs of a query are
+    far fewer than the chip's lanes, and a group's chain (126 doublings + ~60
+    additions per member) is long -- split until the launch has ~32k lanes.
+    The rule rests on the kernel's stand-alone time only.  At the 1-GPU
+    query (18,630 pairs of 10 members), alone on the chip: 1 lane 19.3 ms,
+    2 lanes 10.7 ms, 4 lanes 11.0 ms.  End to end, beside the other streams'
+    kernels, 1 and 2 lanes are indistinguishable; 2 is kept for a U stream
+    that runs alone.  Each split repeats the group's doublings, and 4 lanes
+    cost 3 to 5 ms more per query (tools/ygroup_micro.py,
+    profiles/ygroup/README.md)."""
+    if not on_gpu:
+        return 1
+    sp = 1
+    while sp < 16 and n * sp < 32768:
+        sp *= 2
+    return sp
+
+
+def rp_u_group(table: torch.Tensor, split: torch.Tensor, idx: torch.Tensor, start: torch.Tensor,
+               length: torch.Tensor, G: int, nq: int, S: int, out: torch.Tensor, pad: int,
+               pos: torch.Tensor | None = None, sp: int | None = None) -> torch.Tensor:
+    """Key-group combinations: out[v*pad + g] = affine(sum_k c_(q_k // S) U_(v, q_k)),
+    q_k = idx[start[g] + k], k < length[g], for every verifier v < G and
+    group g.  ``table``: the signed joint table of the G * nq rows U (sign of
+    row v nq + q: ``split[q // S, 8]``); ``split`` [n, 9]: ``glv_split`` of the
+    proofs' challenges c; ``idx`` (int32, values < nq) lists the groups'
+    members.  ``pos`` as in ``rp_u_joint``; ``sp``: lanes per (v, g)
+    (a power of two <= 64; chosen by ``rp_u_group_lanes`` when None)."""
+    ng = start.numel()
+    assert _rows(table, 32) == G * nq * G2_JOINT_ENTRIES and _rows(split, 9) * S >= nq
+    assert idx.dtype == torch.int32 and start.dtype == torch.int64 and length.dtype == torch.int32
+    assert length.numel() == ng and out.is_contiguous() and pad >= ng
+    if pos is None:
+        assert _rows(out, 32) >= (G - 1) * pad + ng
+    else:
+        assert pos.dtype == torch.int64 and pos.numel() == G * ng and pos.device == out.device
+    g, s = _ctx(table, split, idx, start, length, out)
+    if sp is None:
+        sp = rp_u_group_lanes(G * ng, bool(g))
+    assert sp >= 1 and 64 % sp == 0
+    tmp = None if g else torch.empty((G * ng * sp, 48), dtype=torch.int32)
+    _call("dx_rp_u_group", g, s, _ptr(table), _ptr(split.contiguous()), _ptr(idx), _ptr(start), _ptr(length),
+          _ptr(out), ng, G, nq, S, sp, pad, _ptr(pos), _ptr(tmp))
     return out
 
 

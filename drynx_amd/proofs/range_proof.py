@@ -867,7 +867,8 @@ def verify_range_proof_list(rpl: RangeProofList, sigmat: SigMaterial, P_point, t
 
 
 def verify_range_proof_list_multi(r: RangeProofList, sigmat: SigMaterial, P_point, n_vn: int = 1, device=None,
-                                  mode: int = 0, coins: list | None = None, segs: list | None = None) -> list:
+                                  mode: int = 0, coins: list | None = None, segs: list | None = None,
+                                  ygroup: bool | None = None) -> list:
     """``n_vn`` independent batch verifications of one proof list -- one per
     verifying node hosted on this rank, each with its own random weights
     drawn from its own ``coins[v]`` (crypto/coins.py; fresh CSPRNG output
@@ -896,7 +897,11 @@ def verify_range_proof_list_multi(r: RangeProofList, sigmat: SigMaterial, P_poin
     own Miller partial products -- no extra pairing work), and only a VN
     whose batch FAILS pays a second, segment-grouped pass over the cheap
     sides (R MSM, multi-exponentiation, D-check, exponent sums) with the same
-    weights: blame costs ~one VN's MSMs, not a bisection of re-verifications."""
+    weights: blame costs ~one VN's MSMs, not a bisection of re-verifications.
+
+    ``ygroup``: the key-grouped U side (``_msm_queue``) is used where it pays
+    (``_YGROUP_MIN_MULT`` proofs per key) -- None: on a GPU only; True: for
+    host tensors too; False: never."""
     nseg = len(segs) if segs else 1
     if segs is not None:
         assert sum(segs) == len(r) and all(c > 0 for c in segs)
@@ -1053,14 +1058,21 @@ def verify_range_proof_list_multi(r: RangeProofList, sigmat: SigMaterial, P_poin
     # MSM before the U side measured neutral on the pool parts and +2.5 ms on
     # the 1-GPU query: the two chains only slow each other down on the shared
     # CUs; here both are queued before the inputs.)
+    # DPs answering the same columns pair the same keys: one Miller loop per
+    # key instead of one per (proof, key) when that pays (``_msm_queue``)
+    yg = None
+    if (aux is not None if ygroup is None else ygroup) and len(r.cols) == n \
+            and len(set(r.cols)) * _YGROUP_MIN_MULT <= n:       # distinct keys = S * distinct columns
+        yg = dict(groups=_key_groups(r.cols, S, sigmat.n_cols, device), challenge=r.challenge,
+                  y_jac=sigmat.y_jac.to(device))
     if aux is not None:
         with timers.span("rp.verify.msm_queue"):
-            msq = _msm_queue(_inputs, r.V, ab_all, G, n, S, l, vstream, segs, table)
+            msq = _msm_queue(_inputs, r.V, ab_all, G, n, S, l, vstream, segs, table, ygroup=yg)
             for v, uok in zip(vns, msq["u_ok"]):
                 v["u_ok"] = uok
         ev_u = torch.cuda.Event()                                       # the U side's fold is queued
         ev_u.record(torch.cuda.current_stream(device))
-    else:
+    elif yg is None:
         _inputs()
     with timers.span("rp.verify.passes"), (torch.cuda.stream(aux) if aux is not None else _nullctx()):
         Cp, z = _zcp()
@@ -1084,7 +1096,7 @@ def verify_range_proof_list_multi(r: RangeProofList, sigmat: SigMaterial, P_poin
             else:
                 dcheck = nt.g1_msm_device(dpts, dsc, n, ((n, 254),) * (2 * G))     # group = row // n
     if aux is None:  # host: the U side after the passes
-        msq = _msm_queue(inp["Y"], r.V, ab_all, G, n, S, l, None, segs)
+        msq = _msm_queue(inp.get("Y", _inputs), r.V, ab_all, G, n, S, l, None, segs, ygroup=yg)
         for v, uok in zip(vns, msq["u_ok"]):
             v["u_ok"] = uok
     useg = fR = None
@@ -1110,7 +1122,7 @@ def verify_range_proof_list_multi(r: RangeProofList, sigmat: SigMaterial, P_poin
         if useg is None:
             useg = _seg_products(msq)                                  # [G, nseg, 96] host
         for k_, v in enumerate(vns):
-            v["F"] = nt.gt_prod(useg[k_].view(nseg, 1, 96), chunk=64).view(1, 96)
+            v["F"] = nt.gt_prod(useg[k_].view(-1, 1, 96), chunk=64).view(1, 96)
         if fR is None:
             fR, rok = _msm_r_miller(hR, S_R)
         for v, f, ok in zip(vns, fR, rok):
@@ -1164,6 +1176,9 @@ def verify_range_proof_list_multi(r: RangeProofList, sigmat: SigMaterial, P_poin
     redo = [k_ for k_ in range(G) if not out[k_] or (seg_valid is not None and not masked)]
     res = [([True] * nseg if seg_valid is None else list(seg_valid)) if ok else None for ok in out]
     if redo:
+        if "items" in msq:  # key-grouped first pass: the per-segment U-side products only now
+            with timers.span("rp.verify.useg_items"):
+                useg = _useg_items(msq)
         with timers.span("rp.verify.segments"):
             x = dict(A2=A2, rho=rho_all, ab=ab_all, gam=gam_all, w=w_all, Cp=Cp, z=z, useg=useg, u_seg=msq["u_seg"],
                      # the segment pass keeps host-planned 11-bit windows (its groups are
@@ -1312,8 +1327,55 @@ def _r_window(m: int, G: int) -> int:
     return min(range(8, 14), key=lambda c: -(-254 // c) * (m + 8 * (1 << c)))
 
 
+# Proofs per key (n*S / distinct keys) from which the key-grouped U side is
+# used.  At the 1-GPU query's 186,300 U rows the per-item fold takes 25.0 to
+# 25.3 ms alone on the chip; signed table + key-group combination + fold over
+# the keys 24.1 to 24.3 ms at 2 proofs per key, 19.9 at 3, 20.1 at 4, 18.3 at
+# 10 (tools/ygroup_micro.py, two runs: profiles/ygroup/README.md).  The
+# smallest multiplicity with a measured gain is 2 (0.7 and 1.2 ms, besides
+# the 0.9 ms of c_p y products), plus one.
+_YGROUP_MIN_MULT = 3
+_KEY_GROUPS: dict = {}
+_KEY_GROUPS_MAX = 8
+
+
+def _key_groups(cols, S: int, n_cols: int, device) -> dict:
+    """The U rows q = p*S + i of a proof list grouped by their G1 key
+    ``y_idx = i * n_cols + cols[p]``: "idx" (int32 [n*S], the q's sorted by
+    group), "start" / "len" per group, "keys" (the groups' y_idx) and "ng".
+    Host-built (numpy) from the host-side columns, uploaded through pinned
+    memory and cached per (columns, S, n_cols, device) with the discipline of
+    ``_shape_index``: published when built, every reading stream recorded,
+    the device drained before entries are dropped.  Called only for lists
+    that take the grouped path (the caller counts the distinct columns
+    first): a pool slice or a bisection sub-list with ~1 proof per key adds
+    no upload or synchronisation and evicts nothing."""
+    dev = torch.device(device)
+    c = np.asarray(cols, dtype=np.int64)
+    k = (c.tobytes(), S, n_cols, str(dev))
+    kg = _KEY_GROUPS.get(k)
+    if kg is None:
+        if len(_KEY_GROUPS) >= _KEY_GROUPS_MAX:
+            if dev.type == "cuda":
+                torch.cuda.synchronize(dev)
+            _KEY_GROUPS.clear()
+        y_idx = (np.arange(S).reshape(1, S) * n_cols + c.reshape(-1, 1)).reshape(-1)
+        keys, inv = np.unique(y_idx, return_inverse=True)
+        inv = inv.reshape(-1)
+        ln = np.bincount(inv, minlength=len(keys))
+        ts = [_h2d(np.argsort(inv, kind="stable").astype(np.int32), dev),
+              _h2d((np.cumsum(ln) - ln).astype(np.int64), dev), _h2d(ln.astype(np.int32), dev),
+              _h2d(keys.astype(np.int64), dev)]
+        bn.publish(ts)
+        kg = _KEY_GROUPS[k] = dict(idx=ts[0], start=ts[1], len=ts[2], keys=ts[3], ng=len(keys))
+    if dev.type == "cuda":
+        for t in (kg["idx"], kg["start"], kg["len"], kg["keys"]):
+            t.record_stream(torch.cuda.current_stream(dev))  # a later drop waits for this reader
+    return kg
+
+
 def _msm_queue(Y, V, ab_all, G: int, n: int, S: int, L: int, vstream=None, segs: list | None = None,
-               table=None) -> dict:
+               table=None, ygroup: dict | None = None) -> dict:
     """Verifier mode "msm", the U side (no host sync; csrc/kernels/dx_rpmsm.hip):
     the pairing side of G verifiers' batches regrouped by bilinearity,
         prod_it ML(rho_it (Zphi_pj B - Y_pi), V_it)
@@ -1327,45 +1389,36 @@ def _msm_queue(Y, V, ab_all, G: int, n: int, S: int, L: int, vstream=None, segs:
     workgroup partial products ("fb"), reduced per (VN, segment) by
     ``_seg_products``; host: per-item Miller loops over the same pairs.
     "u_seg": [G, n_segments] exact G2 membership of every segment's U's.
-    ``Y`` may be a callable returning it (issued after the U combinations)."""
+    ``Y`` may be a callable returning it (issued after the U combinations).
+
+    ``ygroup`` (``_key_groups`` of the proofs' columns as "groups", their
+    "challenge" rows and the keys "y_jac"): Y_q = c_p y_k with the same key
+    y_k for every proof of a key group, so
+        prod_(q in k) ML(-c_p y_k, U_vq) ~ ML(-y_k, sum_(q in k) c_p U_vq):
+    one Miller loop per (VN, key) over the key-group combinations
+    (``nt.rp_u_group``) and no c_p y products.  Every U_vq is still computed
+    and tested for G2 membership ("u_seg" as above); the queue then returns
+    the per-VN product only (sb = [0]) and keeps what ``_useg_items`` needs
+    for the per-segment products of a failing batch ("items")."""
     dev = V.device
     nq = n * S
-    nseg = len(segs) if segs else 1
     qoff = np.cumsum([0] + [c * S for c in segs]) if segs else np.array([0, nq])
     cq = np.diff(qoff)
     if table is None:
         with timers.span("rp.u.joint_table"):
             table = nt.g2_joint_table(V)
     out = {"G": G}
-    if dev.type == "cuda":
-        if nseg == 1:
-            K = fold_k(G * (nq + 1))
-            rows = 64 * K
-            pad = -(-(nq + 1) // rows) * rows
-        else:
-            K = fold_k(G * nq)
-            rows = 64 * K
-            ac = -(-cq // rows) * rows                              # segments start whole workgroups
-            segbase = np.cumsum(ac) - ac
-            pad = int(ac.sum())
-        period = -(-(G * pad) // (rows * nt.FOLD_P_ALIGN)) * (rows * nt.FOLD_P_ALIGN)
-        # a small batch (a pool slice) folds on three lanes per item over the
-        # raw line coefficients and affine points (-Y); a large one keeps the
-        # one-lane accumulation over normalised lines and (x/y, 1/y) points
-        # (the three-lane fold at the 1-GPU size: no faster, profiles/r6/ab/)
-        coop = K == 1 and G * pad <= _COOP_MAX_ITEMS
+    lay = pos = None
+    if dev.type == "cuda" and ygroup is None:
+        lay = _fold_layout(G, nq, cq, dev)
+        pad, pos = lay["pad"], lay["pos"]
         Uall = torch.zeros((G * pad, 32), dtype=torch.int32, device=dev)
-        UV = torch.zeros((period, 16), dtype=torch.int32, device=dev)
-        pos = None
-        if nseg > 1:
-            # row of (VN v, group q) in the fold layout (segments start whole
-            # workgroups): host-known, one upload before the U kernels -- no
-            # index glue between the combinations and the fold's coefficients
-            qseg = np.repeat(np.arange(nseg), cq)
-            qpos = segbase[qseg] + np.arange(nq) - qoff[:-1][qseg]
-            pos = _h2d((np.arange(G).reshape(G, 1) * pad + qpos.reshape(1, nq)).reshape(-1).astype(np.int64), dev)
-        with timers.span("rp.u.joint"):
-            nt.rp_u_joint(table, ab_all, nq, G, L, Uall, pad, pos)
+    else:
+        pad = nq
+        Uall = torch.zeros((G * nq, 32), dtype=torch.int32, device=dev)
+    with timers.span("rp.u.joint"):
+        nt.rp_u_joint(table, ab_all, nq, G, L, Uall, pad, pos)
+    if dev.type == "cuda":
         # G2 membership of every U (exact test), on the validation stream beside the fold
         cur = torch.cuda.current_stream(dev)
         vs = vstream if vstream is not None else cur
@@ -1381,43 +1434,131 @@ def _msm_queue(Y, V, ab_all, G: int, n: int, S: int, L: int, vstream=None, segs:
         Uall.record_stream(vs)
         if pos is not None:
             pos.record_stream(vs)
-        # the points of the fold (affine -Y_q, or uv(-Y_q) for the normalised
-        # lines), after the U combinations are queued (``Y`` may be the
-        # callable that issues their inputs)
-        if callable(Y):
-            Y = Y()
-        if coop:  # affine -Y_q, the same for every VN
-            negY = nt.g1_to_affine(nt.g1_add(bn.g1_infinity_jac(nq, dev), Y.contiguous(), subtract=True))
-        elif nseg > 1:  # uv(-Y_q) is the same for every VN: computed once, copied per VN below
-            UVd = torch.zeros((nq + 1, 16), dtype=torch.int32, device=dev)
-            nt.rp_msm_uv(Y, UVd, nq, 1, nq + 1)
-            negY = UVd[:nq]
-        if nseg == 1:
-            if coop:
-                UV[: G * pad].view(G, pad, 16)[:, :nq] = negY
-            else:
-                nt.rp_msm_uv(Y, UV, nq, G, pad)
-        else:
-            UV.index_copy_(0, pos, negY.repeat(G, 1))
-        with timers.span("rp.u.fold"):
-            if coop:
-                out["fb"] = nt.rp_fold_accum_coop_raw(nt.rp_fold_coeffs(Uall), UV, Uall, period, 1)
-            else:
-                out["fb"] = nt.rp_fold_accum_n(nt.rp_fold_ncoeffs(Uall), UV, Uall, period, 1, K)
-        out["blk"] = pad // rows
-        out["sb"] = [0] if nseg == 1 else (segbase // rows).tolist()
-        out["nb"] = [pad // rows] if nseg == 1 else (ac // rows).tolist()
     else:
-        if callable(Y):
-            Y = Y()
-        Uall = torch.zeros((G * nq, 32), dtype=torch.int32, device=dev)
-        nt.rp_u_joint(table, ab_all, nq, G, L, Uall, nq)
         out["u_seg"] = _seg_all(nt.g2_subgroup(Uall).view(G, nq).bool(), cq, dev)
         out["u_ok"] = [bool(x) for x in out["u_seg"].all(dim=1).tolist()]
-        negY = nt.g1_to_affine(nt.g1_add(bn.g1_infinity_jac(nq, dev), Y.contiguous(), subtract=True))
-        out["fb"] = torch.cat([nt.miller_loop(negY, Uall[v * nq:(v + 1) * nq].contiguous()) for v in range(G)])
-        out["blk"], out["sb"], out["nb"] = nq, qoff[:-1].tolist(), cq.tolist()
+    if ygroup is not None:
+        kg = ygroup["groups"]
+        ng = kg["ng"]
+        with timers.span("rp.u.group"):
+            split = nt.glv_split(ygroup["challenge"].contiguous())       # per proof: k1, |k2|, sign
+            sgn = split[:, 8].repeat_interleave(S).repeat(G).contiguous()
+            tU = nt.g2_joint_table(Uall, sgn)                            # over (U, +-[lambda] U)
+            Yk = ygroup["y_jac"].index_select(0, kg["keys"]).contiguous()
+            if dev.type == "cuda":
+                lay = _fold_layout(G, ng, np.array([ng]), dev)
+                Ug = torch.zeros((G * lay["pad"], 32), dtype=torch.int32, device=dev)
+            else:
+                Ug = torch.zeros((G * ng, 32), dtype=torch.int32, device=dev)
+            nt.rp_u_group(tU, split, kg["idx"], kg["start"], kg["len"], G, nq, S, Ug, Ug.shape[0] // G)
+        if dev.type == "cuda":
+            _fold_items(lay, Ug, Yk, G, ng, out)
+        else:
+            _fold_items_host(Ug, Yk, G, ng, np.array([0, ng]), out)
+        out["items"] = dict(Y=Y, Uall=Uall, nq=nq, qoff=qoff)
+    elif dev.type == "cuda":
+        _fold_items(lay, Uall, Y, G, nq, out)
+    else:
+        _fold_items_host(Uall, Y, G, nq, qoff, out)
     return out
+
+
+def _fold_layout(G: int, nq: int, cq, dev) -> dict:
+    """Rows of the GPU fold for G verifiers' nq pairs in the consecutive
+    segments ``cq``: items per lane K, the per-VN row count "pad" (one
+    segment: room for the (B, R) row; several: each starts whole
+    accumulation workgroups, "pos" = the row of (v, q)), the padded "period"
+    and the partial-product blocks per segment ("sb", "nb")."""
+    nseg = len(cq)
+    pos = None
+    if nseg == 1:
+        K = fold_k(G * (nq + 1))
+        rows = 64 * K
+        pad = -(-(nq + 1) // rows) * rows
+        sb, nb = [0], [pad // rows]
+    else:
+        K = fold_k(G * nq)
+        rows = 64 * K
+        ac = -(-cq // rows) * rows                              # segments start whole workgroups
+        segbase = np.cumsum(ac) - ac
+        pad = int(ac.sum())
+        # row of (VN v, group q) in the fold layout (segments start whole
+        # workgroups): host-known, one upload before the U kernels -- no
+        # index glue between the combinations and the fold's coefficients
+        qoff = np.cumsum(cq) - cq
+        qseg = np.repeat(np.arange(nseg), cq)
+        qpos = segbase[qseg] + np.arange(nq) - qoff[qseg]
+        pos = _h2d((np.arange(G).reshape(G, 1) * pad + qpos.reshape(1, nq)).reshape(-1).astype(np.int64), dev)
+        sb, nb = (segbase // rows).tolist(), (ac // rows).tolist()
+    period = -(-(G * pad) // (rows * nt.FOLD_P_ALIGN)) * (rows * nt.FOLD_P_ALIGN)
+    # a small batch (a pool slice) folds on three lanes per item over the
+    # raw line coefficients and affine points (-Y); a large one keeps the
+    # one-lane accumulation over normalised lines and (x/y, 1/y) points
+    # (the three-lane fold at the 1-GPU size: no faster, profiles/r6/ab/)
+    coop = K == 1 and G * pad <= _COOP_MAX_ITEMS
+    return dict(K=K, rows=rows, pad=pad, period=period, coop=coop, pos=pos, sb=sb, nb=nb)
+
+
+def _fold_items(lay: dict, Uall, Y, G: int, nq: int, out: dict):
+    """The GPU fold of the rows ``Uall`` (layout ``lay``) with the points
+    -Y_q (affine, or uv(-Y_q) for the normalised lines), issued after the U
+    combinations are queued (``Y`` may be the callable that issues their
+    inputs) -> out "fb", "blk", "sb", "nb"."""
+    dev = Uall.device
+    K, rows, pad, period, coop, pos = (lay[k] for k in ("K", "rows", "pad", "period", "coop", "pos"))
+    UV = torch.zeros((period, 16), dtype=torch.int32, device=dev)
+    if callable(Y):
+        Y = Y()
+    if coop:  # affine -Y_q, the same for every VN
+        negY = nt.g1_to_affine(nt.g1_add(bn.g1_infinity_jac(nq, dev), Y.contiguous(), subtract=True))
+    elif pos is not None:  # uv(-Y_q) is the same for every VN: computed once, copied per VN below
+        UVd = torch.zeros((nq + 1, 16), dtype=torch.int32, device=dev)
+        nt.rp_msm_uv(Y, UVd, nq, 1, nq + 1)
+        negY = UVd[:nq]
+    if pos is None:
+        if coop:
+            UV[: G * pad].view(G, pad, 16)[:, :nq] = negY
+        else:
+            nt.rp_msm_uv(Y, UV, nq, G, pad)
+    else:
+        UV.index_copy_(0, pos, negY.repeat(G, 1))
+    with timers.span("rp.u.fold"):
+        if coop:
+            out["fb"] = nt.rp_fold_accum_coop_raw(nt.rp_fold_coeffs(Uall), UV, Uall, period, 1)
+        else:
+            out["fb"] = nt.rp_fold_accum_n(nt.rp_fold_ncoeffs(Uall), UV, Uall, period, 1, K)
+    out["blk"], out["sb"], out["nb"] = pad // rows, lay["sb"], lay["nb"]
+
+
+def _fold_items_host(Uall, Y, G: int, nq: int, qoff, out: dict):
+    """Host: one Miller loop per pair (-Y_q, U_vq), rows v * nq + q."""
+    if callable(Y):
+        Y = Y()
+    negY = nt.g1_to_affine(nt.g1_add(bn.g1_infinity_jac(nq, Uall.device), Y.contiguous(), subtract=True))
+    out["fb"] = torch.cat([nt.miller_loop(negY, Uall[v * nq:(v + 1) * nq].contiguous()) for v in range(G)])
+    out["blk"], out["sb"], out["nb"] = nq, qoff[:-1].tolist(), np.diff(qoff).tolist()
+
+
+def _useg_items(msq: dict) -> torch.Tensor:
+    """Per-(VN, segment) U-side products of a key-grouped queue, on demand
+    (a VN's batch failed: ``_segment_pass`` / ``_segment_hinted`` need them):
+    the per-item fold over the retained U rows and -c_p y -> host [G, k, 96].
+    After the final exponentiation they multiply to the grouped product."""
+    it, G = msq["items"], msq["G"]
+    Uall, nq, qoff = it["Uall"], it["nq"], it["qoff"]
+    out = {"G": G}
+    if Uall.is_cuda:
+        lay = _fold_layout(G, nq, np.diff(qoff), Uall.device)
+        pos = lay["pos"]
+        if pos is None:
+            pos = (torch.arange(G, device=Uall.device).view(G, 1) * lay["pad"]
+                   + torch.arange(nq, device=Uall.device).view(1, nq)).reshape(-1)
+        U = torch.zeros((G * lay["pad"], 32), dtype=torch.int32, device=Uall.device)
+        U.index_copy_(0, pos, Uall)
+        _fold_items(lay, U, it["Y"], G, nq, out)
+    else:
+        _fold_items_host(Uall, it["Y"], G, nq, qoff, out)
+    return _seg_products(out)
 
 
 def _h2d(a, dev) -> torch.Tensor:
