@@ -157,11 +157,11 @@ _SIGS = {
     "dx_msm_keys": [_I, _P, _P, _P, _L, _L, _I, _I, _P, _P],
     "dx_gls8_entries": [],
     "dx_g2_gls8_table": [_I, _P, _P, _P, _P, _L],
-    "dx_gt_gls8_table": [_I, _P, _P, _P, _P, _L],
+    "dx_gt_gls8_table": [_I, _P, _P, _P, _P, _L, _P, _L],
     "dx_g2_gls8_mul": [_I, _P, _P, _P, _P, _P, _L],
-    "dx_rp_prove_a_gls8": [_I, _P, _P, _P, _P, _P, _P, _P, _L, _I, _I, _I],
+    "dx_rp_prove_a_gls8": [_I, _P, _P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _P],
     "dx_gt16_entries": [],
-    "dx_gt16_table": [_I, _P, _P, _P],
+    "dx_gt16_table": [_I, _P, _P, _P, _P],
 }
 
 
@@ -673,14 +673,20 @@ def g2_gls8_table(base_aff: torch.Tensor, out: torch.Tensor | None = None) -> to
 
 
 def gt_gls8_table(bases: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
-    """GLS-2 signed 8-bit fixed-base table(s) [n_bases*2176, 96] of GT elements (816 KiB per base)."""
+    """GLS-2 signed 8-bit fixed-base table(s) [n_bases*2176, 48] of GT elements
+    as torus images beta = (1 + g) / h (csrc/bn254/gt_torus.h; 408 KiB per
+    base).  A base 1 (the set's padding point) gets rows of 0xFFFFFFFF words,
+    which the prover skips; a base -1 has no image: the native call fails (rc 2)."""
     bases = bases.contiguous()
     nb = _rows(bases, 96)
-    table = out if out is not None else torch.empty((nb * GLS8_ENTRIES, 96), dtype=torch.int32, device=bases.device)
-    assert table.shape == (nb * GLS8_ENTRIES, 96) and table.is_contiguous()
+    table = out if out is not None else torch.empty((nb * GLS8_ENTRIES, 48), dtype=torch.int32, device=bases.device)
+    assert table.shape == (nb * GLS8_ENTRIES, 48) and table.is_contiguous()
     work = torch.empty((nb * 17, 96), dtype=torch.int32, device=bases.device)
     g, s = _ctx(bases, table)
-    _call("dx_gt_gls8_table", g, s, _ptr(bases), _ptr(work), _ptr(table), nb)
+    # GPU path: the Fp12 powers of up to 1024 bases at a time (816 KiB each) before they are normalised
+    tb = min(nb, 1024) if g else 0
+    tmp = torch.empty((tb * GLS8_ENTRIES + 1, 96), dtype=torch.int32, device=bases.device) if g else None
+    _call("dx_gt_gls8_table", g, s, _ptr(bases), _ptr(work), _ptr(table), nb, _ptr(tmp), tb)
     return table
 
 
@@ -698,8 +704,8 @@ _gt16: dict = {}
 
 
 def gt16_table(device) -> torch.Tensor:
-    """gT with signed 16-bit windows: [17 * 32768, 96], gT^(d 2^(16w)) (214 MB,
-    built once per device; csrc/kernels/dx_gls8.hip)."""
+    """gT with signed 16-bit windows: [17 * 32768, 48], the torus images of
+    gT^(d 2^(16w)) (107 MB, built once per device; csrc/kernels/dx_gls8.hip)."""
     key = str(torch.device(device))
     if key not in _gt16:
         from ..crypto import bn254 as _bn
@@ -713,9 +719,10 @@ def gt16_table(device) -> torch.Tensor:
                 g = g * g
         pow2 = _bn.gt_tensor(pows, device)
         n = _load().dx_gt16_entries()
-        table = torch.empty((n, 96), dtype=torch.int32, device=pow2.device)
+        table = torch.empty((n, 48), dtype=torch.int32, device=pow2.device)
         gg, s = _ctx(pow2, table)
-        _call("dx_gt16_table", gg, s, _ptr(pow2), _ptr(table))
+        tmp = torch.empty((n + 1, 96), dtype=torch.int32, device=pow2.device) if gg else None
+        _call("dx_gt16_table", gg, s, _ptr(pow2), _ptr(table), _ptr(tmp))
         _gt16[key] = table
     return _gt16[key]
 
@@ -1352,9 +1359,10 @@ def rp_prove_a_tab(gphi_tables, tab_idx, e_sc, t_sc, gt_table, S: int, L: int, w
     g, s = _ctx(gphi_tables, tab_idx, e_sc, t_sc, gt_table)
     if wbits == 7:
         assert tab_idx.dtype == torch.int32 and tab_idx.numel() == n and n % (S * L) == 0
-        t16 = gt16_table(e_sc.device) if e_sc.is_cuda else None                # gT^t in 17 products
+        t16 = gt16_table(e_sc.device) if e_sc.is_cuda else None                # gT^t in 17 steps
+        tmp = torch.empty_like(out) if g else None                             # the finish pass's prefixes and norms
         _call("dx_rp_prove_a_gls8", g, s, _ptr(gphi_tables), _ptr(tab_idx), _ptr(e_sc), _ptr(t_sc),
-              _ptr(t16 if t16 is not None else gt_table), _ptr(out), n, S, L, int(t16 is not None))
+              _ptr(t16 if t16 is not None else gt_table), _ptr(out), n, S, L, int(t16 is not None), _ptr(tmp))
         return out
     if wbits == 6:
         _call("dx_rp_prove_a_gls6", g, s, _ptr(gphi_tables), _ptr(tab_idx), _ptr(e_sc), _ptr(t_sc), _ptr(gt_table),

@@ -257,9 +257,10 @@ class SigMaterial:
         """Prover comb-table layout for this signature set on ``device``:
         8 (8-bit combs, 4 MiB per distinct point: few distinct points, e.g.
         InitRangeProofSignatureDeterministic), 7 (GLS-2 tables with signed
-        8-bit windows, 1.09 MiB per point, 34 additions per evaluation: the
-        reference's random per-CN, per-column keys -- 99,360 points for a
-        SPECTF-shaped query with 3 CNs and u = 16, ~111 GB of HBM), 6 (GLS-2
+        8-bit windows, GT entries as 192-byte torus images, 0.66 MiB per point,
+        34 additions per evaluation: the reference's random per-CN, per-column
+        keys -- 99,360 points for a SPECTF-shaped query with 3 CNs and u = 16,
+        ~70 GB of HBM), 6 (GLS-2
         with unsigned 6-bit windows, 693 KiB per point, 44 additions), 4 (4-bit
         combs, 480 KiB per point, 64 additions) or 0 (no
         tables: variable-base G2 + one pairing per item).  Budgets:
@@ -267,8 +268,8 @@ class SigMaterial:
         host) and ``DRYNX_PROVER_TABLE4_MB`` (GLS / 4-bit layouts, default: the
         free HBM minus the verifier's reserve ``DRYNX_VERIFY_RESERVE_GB`` = 48,
         at most 85% of it / 64 MiB on the host): a 3-CN SPECTF-shaped set
-        (99,360 points) takes the GLS-8 layout (~111 GB), a 6-CN one (198,720
-        points) the GLS-6 one (~138 GB)."""
+        (99,360 points) takes the GLS-8 layout (~70 GB), and so does a 6-CN one
+        (198,720 points, ~138 GB) where that much is free."""
         dev = torch.device(device)
         key = ("mode", str(dev))
         if key in self._ptab:
@@ -292,7 +293,7 @@ class SigMaterial:
             mode = int(forced)
         elif n * (4 << 20) <= b8:
             mode = 8
-        elif n * nt.GLS8_ENTRIES * (128 + 384) <= b4:
+        elif n * nt.GLS8_ENTRIES * (128 + 192) <= b4:
             mode = 7
         elif n * nt.GLS6_ENTRIES * (128 + 384) <= b4:
             mode = 6
@@ -361,7 +362,7 @@ class SigMaterial:
                                  6: (nt.GLS6_ENTRIES, nt.g2_gls6_table, nt.gt_gls6_table),
                                  7: (nt.GLS8_ENTRIES, nt.g2_gls8_table, nt.gt_gls8_table)}[mode]
             g2 = torch.empty((n * E, 32), dtype=torch.int32, device=dev)
-            gt = torch.empty((n * E, 96), dtype=torch.int32, device=dev)
+            gt = torch.empty((n * E, 48 if mode == 7 else 96), dtype=torch.int32, device=dev)  # 7: torus images
             A = self.A.to(dev)
             step = 8192
             shard = getattr(self, "_shard", None)

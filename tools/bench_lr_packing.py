@@ -58,7 +58,7 @@ def table_plan(args, device) -> str | None:
 
     n_out = [lr_nbr_outputs(args.features, 2, p) for p in LAYOUTS.values()]
     points = args.cns * args.u * sum(n_out)
-    tables = points * nt.GLS8_ENTRIES * (128 + 384)
+    tables = points * nt.GLS8_ENTRIES * (128 + 192)
     reserve = int((48 << 30) * max(1.0, args.dps * n_out[0] / HEADLINE_PROOFS))
     if tables + reserve <= torch.cuda.mem_get_info(device)[0]:
         return None
