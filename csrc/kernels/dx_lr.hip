@@ -37,6 +37,13 @@
 // same instantiations but not the tile-blocks strictly below the diagonal
 // (unless they hold row D), and dx_lr_reduce_pack does block sum, gather of
 // [level 1, upper triangle] and the rounding to int64 in one launch.
+//
+// Several label columns (query extension NbrTargets = T): level 2's weight
+// y - y (-1)^2 - 1 = -1 does not depend on the label, so T binary models over
+// the same records share it.  dx_lr_encode_multi (the kMulti instantiations)
+// accumulates level 1 of target t, g_t = 2 Y[i][t] - 1, in row D + t: in the
+// spare rows of the one 48-row tile-block while D + T <= 48, in further row
+// tiles beyond.  The single-label instantiations are untouched by it.
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <cstdio>
@@ -62,6 +69,11 @@ struct LrArgs {
   const double *y;     // [N] labels (double) or null
   double wa, wb;
   int level1;          // 1: g = 2y - 1 accumulated in row D
+  // multi-target encoder only (kMulti kernels): T label columns, level 1 of
+  // target t in row D + t, level-2 weight the constant wb
+  const double *Y;     // [N][T] labels (double), row stride ldy
+  int64_t ldy;
+  int T;               // level-1 rows (1 for the single-label entry points)
 };
 
 // Where one launch's tile-blocks sit in the PxP output: block (x, y, z) covers
@@ -73,7 +85,11 @@ struct LrGrid {
 
 // kDiag: every tile-block of the launch is on the diagonal (the single 3x3
 // tile-block of a narrow input): no B-side state at all.
-template <int TA, int TB, bool kDiag>
+// kMulti: T label columns (p.Y) instead of one (p.y): the A operand of row
+// D + t is g_t = 2 Y[i][t] - 1, every other row is xa * wb.  The B operand,
+// the K-step order, the record striding and the reductions are those of the
+// single-label kernel, so each output element is the same bits as there.
+template <int TA, int TB, bool kDiag, bool kMulti = false>
 __global__ void __launch_bounds__(256) lr_encode_kernel(LrArgs p, double *__restrict__ partial, LrGrid g) {
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
@@ -100,6 +116,13 @@ __global__ void __launch_bounds__(256) lr_encode_kernel(LrArgs p, double *__rest
     mua[t] = (raw && p.mean) ? p.mean[srca[t]] : 0.0;
     sda[t] = (raw && p.sd) ? p.sd[srca[t]] : 1.0;
   }
+  // kMulti: the label column whose level 1 this lane's row of tile t carries, or -1
+  int tcol[TA];
+#pragma unroll
+  for (int t = 0; t < TA; t++) {
+    const int c = (ta + t) * kTile + col;
+    tcol[t] = (kMulti && c >= D && c < D + p.T) ? c - D : -1;
+  }
 #pragma unroll
   for (int t = 0; t < TB; t++) {
     const int c = (tb + t) * kTile + col;
@@ -116,10 +139,21 @@ __global__ void __launch_bounds__(256) lr_encode_kernel(LrArgs p, double *__rest
     const int64_t row = s * 4 + kk;
     double va[TA], vb[TB];
     double wi = 0.0, gi = 0.0;
+    double ga[TA];
+#pragma unroll
+    for (int t = 0; t < TA; t++) ga[t] = 0.0;
     if (row < p.N) {
-      const double yi = p.y ? p.y[row] : 0.0;
-      wi = p.w ? p.w[row] : p.wa * yi + p.wb;
-      gi = 2.0 * yi - 1.0;
+      if constexpr (kMulti) {
+        wi = p.wb;
+        const double *yr = p.Y + row * p.ldy;
+#pragma unroll
+        for (int t = 0; t < TA; t++)
+          if (tcol[t] >= 0) ga[t] = 2.0 * yr[tcol[t]] - 1.0;
+      } else {
+        const double yi = p.y ? p.y[row] : 0.0;
+        wi = p.w ? p.w[row] : p.wa * yi + p.wb;
+        gi = 2.0 * yi - 1.0;
+      }
       const double *xr = p.X + row * p.ldx;
 #pragma unroll
       for (int t = 0; t < TA; t++) {
@@ -150,7 +184,7 @@ __global__ void __launch_bounds__(256) lr_encode_kernel(LrArgs p, double *__rest
 #pragma unroll
     for (int a = 0; a < TA; a++) {
       const int c = (ta + a) * kTile + col;  // global row of the output
-      const double av = (p.level1 && c == D) ? gi : va[a] * wi;
+      const double av = kMulti ? (tcol[a] >= 0 ? ga[a] : va[a] * wi) : ((p.level1 && c == D) ? gi : va[a] * wi);
 #pragma unroll
       for (int b = 0; b < TB; b++) acc[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, vb[b], acc[a][b], 0, 0, 0);
     }
@@ -173,67 +207,83 @@ __global__ void __launch_bounds__(256) lr_encode_kernel(LrArgs p, double *__rest
   }
 }
 
-template <int TA, int TB, bool kDiag = false>
+template <int TA, int TB, bool kDiag = false, bool kMulti = false>
 void launch_tiles(hipStream_t stream, const LrArgs &a, double *partial, int n_blocks, int ta0, int tb0, int nga,
                   int ngb, int P) {
   if (nga <= 0 || ngb <= 0) return;
   const LrGrid g{ta0, tb0, P};
-  hipLaunchKernelGGL((lr_encode_kernel<TA, TB, kDiag>), dim3(n_blocks, nga, ngb), dim3(256), 0, stream, a, partial,
+  hipLaunchKernelGGL((lr_encode_kernel<TA, TB, kDiag, kMulti>), dim3(n_blocks, nga, ngb), dim3(256), 0, stream, a, partial,
                      g);
 }
 
 // run-time tile-block shape (tan x tbn tiles, each 1..3; 0 = nothing to launch) -> instantiation
-template <int TA>
+template <int TA, bool kMulti>
 void launch_cols(hipStream_t stream, const LrArgs &a, double *partial, int n_blocks, int ta0, int tb0, int nga,
                  int ngb, int P, int tbn) {
-  if (tbn == 1) launch_tiles<TA, 1>(stream, a, partial, n_blocks, ta0, tb0, nga, ngb, P);
-  else if (tbn == 2) launch_tiles<TA, 2>(stream, a, partial, n_blocks, ta0, tb0, nga, ngb, P);
-  else if (tbn == 3) launch_tiles<TA, 3>(stream, a, partial, n_blocks, ta0, tb0, nga, ngb, P);
+  if (tbn == 1) launch_tiles<TA, 1, false, kMulti>(stream, a, partial, n_blocks, ta0, tb0, nga, ngb, P);
+  else if (tbn == 2) launch_tiles<TA, 2, false, kMulti>(stream, a, partial, n_blocks, ta0, tb0, nga, ngb, P);
+  else if (tbn == 3) launch_tiles<TA, 3, false, kMulti>(stream, a, partial, n_blocks, ta0, tb0, nga, ngb, P);
 }
 
+template <bool kMulti>
 void launch_rows(hipStream_t stream, const LrArgs &a, double *partial, int n_blocks, int ta0, int tb0, int nga,
                  int ngb, int P, int tan, int tbn) {
-  if (tan == 1) launch_cols<1>(stream, a, partial, n_blocks, ta0, tb0, nga, ngb, P, tbn);
-  else if (tan == 2) launch_cols<2>(stream, a, partial, n_blocks, ta0, tb0, nga, ngb, P, tbn);
-  else if (tan == 3) launch_cols<3>(stream, a, partial, n_blocks, ta0, tb0, nga, ngb, P, tbn);
+  if (tan == 1) launch_cols<1, kMulti>(stream, a, partial, n_blocks, ta0, tb0, nga, ngb, P, tbn);
+  else if (tan == 2) launch_cols<2, kMulti>(stream, a, partial, n_blocks, ta0, tb0, nga, ngb, P, tbn);
+  else if (tan == 3) launch_cols<3, kMulti>(stream, a, partial, n_blocks, ta0, tb0, nga, ngb, P, tbn);
 }
 
-// Padded output width: 48 while level 2 and the level-1 row fit one 3x3
-// tile-block, the tile-padded row count beyond that.
+// Padded output width: 48 while level 2 and the level-1 rows (one per label
+// column) fit one 3x3 tile-block, the tile-padded row count beyond that.
 int lr_padded(int D, int level1) {
-  const int nt = (D + (level1 ? 1 : 0) + kTile - 1) / kTile;
+  const int nt = (D + level1 + kTile - 1) / kTile;
   return nt <= kTiles ? kD : nt * kTile;
 }
 
+// Live tiles: rows 0..D+T-1 (level 2, then one level-1 row per label column),
+// columns 0..D-1.  Up to 48 rows are the single diagonal 3x3 tile-block with
+// the level-1 rows in its spare rows; beyond that the row tiles (ntr) and the
+// column tiles (ntc <= ntr) are cut independently into full 3x3 tile-blocks
+// and the ragged right column / bottom row / corner, so fb = 0 (a few columns
+// under many level-1 rows) and rb = 0 with ra > 0 (level-1 rows that open a
+// row tile of their own) are launches with an empty side, not special cases.
+//
 // upper: the plan of the packed (distinct-coefficient) layout, which reads
-// level 2 only at (i, j), i <= j, and the level-1 row D.  Tile-block (Y, Z) of
-// the 3x3 grid lies strictly below the diagonal when Y > Z; row D sits in the
-// last row tile, hence in the last tile-block row, which is launched whole.
+// level 2 only at (i, j), i <= j, and the level-1 rows D..D+T-1.  Tile-block
+// (Y, Z) of the 3x3 grid lies strictly below the diagonal when Y > Z; a
+// tile-block row that holds any row >= D (48 (Y + 1) > D) is launched whole,
+// from column tile 0.  With one level-1 row that is the last full tile-block
+// row when there is no ragged bottom row, and none otherwise.  The ragged
+// bottom row holds the last live row, hence level-1 rows: always whole.  The
+// ragged right column (block column fb) is on or above the diagonal for
+// Y <= fb and belongs to an all-level-1 tile-block row for Y > fb (D <=
+// 48 fb + 16 rb < 48 Y): always launched.
 // Every launched tile-block is the same instantiation over the same record
 // blocks as in the full plan, so what it writes is the same bits.
+template <bool kMulti>
 int launch(void *stream_, const LrArgs &a, double *partial, int n_blocks, int P, bool upper = false) {
   const int D = a.dx + a.aug;
-  if (a.dx <= 0 || n_blocks <= 0 || P != lr_padded(D, a.level1)) return -2;
-  if ((a.level1 || !a.w) && !a.y) return -2;
+  const int l1 = a.level1 ? a.T : 0;
+  if (a.dx <= 0 || n_blocks <= 0 || a.T < 1 || a.T > 64 || P != lr_padded(D, l1)) return -2;
+  if (kMulti ? (!a.Y || a.ldy < 0) : ((a.level1 || !a.w) && !a.y)) return -2;
   hipStream_t stream = (hipStream_t)stream_;
   if (P == kD) {
-    launch_tiles<kTiles, kTiles, true>(stream, a, partial, n_blocks, 0, 0, 1, 1, P);
+    launch_tiles<kTiles, kTiles, true, kMulti>(stream, a, partial, n_blocks, 0, 0, 1, 1, P);
   } else {
-    // live tiles: rows 0..D (with level 1), columns 0..D-1; full 3x3 tile-blocks, then the ragged edges
     const int ntr = P / kTile, ntc = (D + kTile - 1) / kTile;
     const int fa = ntr / kTiles, ra = ntr % kTiles, fb = ntc / kTiles, rb = ntc % kTiles;
     if (!upper) {
-      launch_tiles<kTiles, kTiles>(stream, a, partial, n_blocks, 0, 0, fa, fb, P);
+      launch_tiles<kTiles, kTiles, false, kMulti>(stream, a, partial, n_blocks, 0, 0, fa, fb, P);
     } else {
       for (int Y = 0; Y < fa; Y++) {
-        const int z0 = (a.level1 && ra == 0 && Y == fa - 1) ? 0 : Y;  // the tile-block row of row D: whole
-        launch_tiles<kTiles, kTiles>(stream, a, partial, n_blocks, Y * kTiles, z0 * kTiles, 1, fb - z0, P);
+        const int z0 = (l1 && kD * (Y + 1) > D) ? 0 : Y;  // a tile-block row with level-1 rows: whole
+        launch_tiles<kTiles, kTiles, false, kMulti>(stream, a, partial, n_blocks, Y * kTiles, z0 * kTiles, 1, fb - z0,
+                                                    P);
       }
     }
-    // the ragged right column is at or above the diagonal (fb >= every full Y), the ragged bottom row holds row D
-    launch_rows(stream, a, partial, n_blocks, 0, fb * kTiles, fa, 1, P, kTiles, rb);
-    launch_rows(stream, a, partial, n_blocks, fa * kTiles, 0, 1, fb, P, ra, kTiles);
-    launch_rows(stream, a, partial, n_blocks, fa * kTiles, fb * kTiles, 1, 1, P, ra, rb);
+    launch_rows<kMulti>(stream, a, partial, n_blocks, 0, fb * kTiles, fa, 1, P, kTiles, rb);
+    launch_rows<kMulti>(stream, a, partial, n_blocks, fa * kTiles, 0, 1, fb, P, ra, kTiles);
+    launch_rows<kMulti>(stream, a, partial, n_blocks, fa * kTiles, fb * kTiles, 1, 1, P, ra, rb);
   }
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) {
@@ -248,8 +298,8 @@ int launch(void *stream_, const LrArgs &a, double *partial, int n_blocks, int P,
 // partial: [n_blocks][P][P], P = lr_padded(D, 0).
 extern "C" int dx_lr_moments(void *stream, const double *X, const double *w, int64_t N, int D, double *partial,
                              int n_blocks, int P) {
-  LrArgs a{X, D, N, D, 0, nullptr, nullptr, w, nullptr, 0.0, 0.0, 0};
-  return launch(stream, a, partial, n_blocks, P);
+  LrArgs a{X, D, N, D, 0, nullptr, nullptr, w, nullptr, 0.0, 0.0, 0, nullptr, 0, 1};
+  return launch<false>(stream, a, partial, n_blocks, P);
 }
 
 // Block partials -> totals, for many encoder launches at once: out[i][e] =
@@ -301,8 +351,8 @@ extern "C" int dx_lr_reduce(void *stream, const double *partial, int64_t nb, int
 extern "C" int dx_lr_encode(void *stream, const double *X, int64_t ldx, int64_t N, int dx, const double *mean,
                             const double *sd, const double *y, double wa, double wb, double *partial, int n_blocks,
                             int P) {
-  LrArgs a{X, ldx, N, dx, 1, mean, sd, nullptr, y, wa, wb, 1};
-  return launch(stream, a, partial, n_blocks, P);
+  LrArgs a{X, ldx, N, dx, 1, mean, sd, nullptr, y, wa, wb, 1, nullptr, 0, 1};
+  return launch<false>(stream, a, partial, n_blocks, P);
 }
 
 // The upper launch plan of dx_lr_encode (same arguments, same kernels): the
@@ -312,8 +362,22 @@ extern "C" int dx_lr_encode(void *stream, const double *X, int64_t ldx, int64_t 
 extern "C" int dx_lr_encode_upper(void *stream, const double *X, int64_t ldx, int64_t N, int dx, const double *mean,
                                   const double *sd, const double *y, double wa, double wb, double *partial,
                                   int n_blocks, int P) {
-  LrArgs a{X, ldx, N, dx, 1, mean, sd, nullptr, y, wa, wb, 1};
-  return launch(stream, a, partial, n_blocks, P, true);
+  LrArgs a{X, ldx, N, dx, 1, mean, sd, nullptr, y, wa, wb, 1, nullptr, 0, 1};
+  return launch<false>(stream, a, partial, n_blocks, P, true);
+}
+
+// Multi-target encoder: T label columns over the same records share ONE level
+// 2 (its weight y - y (-1)^2 - 1 = -1 does not depend on the label, so it is
+// the constant wb here), and level 1 of target t, sum_i (2 Y[i][t] - 1) xa_i,
+// rides in row D + t.  Y: [N][T] doubles with row stride ldy; partial:
+// [n_blocks][P][P], P = lr_padded(dx + 1, T); upper != 0: the packed layout's
+// launch plan.  T = 1..64.
+extern "C" int dx_lr_encode_multi(void *stream, const double *X, int64_t ldx, int64_t N, int dx, const double *mean,
+                                  const double *sd, const double *Y, int64_t ldy, int T, double wb, double *partial,
+                                  int n_blocks, int P, int upper) {
+  if (T < 1 || T > 64 || (N > 1 && ldy < T)) return -2;
+  LrArgs a{X, ldx, N, dx, 1, mean, sd, nullptr, nullptr, 0.0, wb, 1, Y, ldy, T};
+  return launch<true>(stream, a, partial, n_blocks, P, upper != 0);
 }
 
 // Block partials -> the packed integer vector a DP encrypts, in one launch:
@@ -325,20 +389,24 @@ extern "C" int dx_lr_encode_upper(void *stream, const double *X, int64_t ldx, in
 // round_precision's fp64 operations (x = v * precision, floor(|x| + 0.5) with
 // the sign of x: half away from zero, 0 for x == +-0), so a packed value is
 // the same bits as the cartesian path's value at (a, c).
+// T label columns (multi-target encoder): the level-1 part is T*D values,
+// target t from row D + t, then the same upper triangle; T = 1 is the layout
+// above.  Reads only (i, j), i <= j < D, and rows D..D+T-1, columns < D.
 namespace {
 __global__ void __launch_bounds__(256) lr_reduce_pack_kernel(const double *__restrict__ partial, int64_t nb, int P,
-                                                             int D, int64_t n_items, double precision,
+                                                             int D, int T, int64_t n_items, double precision,
                                                              int64_t *__restrict__ out, double *__restrict__ fout) {
-  const int64_t n_out = (int64_t)D + (int64_t)D * (D + 1) / 2;
+  const int64_t n_l1 = (int64_t)T * D;
+  const int64_t n_out = n_l1 + (int64_t)D * (D + 1) / 2;
   const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= n_items * n_out) return;
   const int64_t i = t / n_out, e = t % n_out;
   int64_t r, c;
-  if (e < D) {
-    r = D;
-    c = e;
+  if (e < n_l1) {
+    r = D + e / D;
+    c = e % D;
   } else {
-    const int64_t q = e - D;
+    const int64_t q = e - n_l1;
     // row a: the largest a with off(a) = a*D - a(a-1)/2 <= q
     const double m = 2.0 * D + 1.0;
     int64_t a = (int64_t)((m - sqrt(m * m - 8.0 * (double)q)) * 0.5);
@@ -369,20 +437,27 @@ __global__ void __launch_bounds__(256) lr_reduce_pack_kernel(const double *__res
 }
 }  // namespace
 
-// partial: [n_items][nb][P][P]; out: int64 [n_items][D + D(D+1)/2]; fout: the
+// partial: [n_items][nb][P][P]; out: int64 [n_items][T*D + D(D+1)/2]; fout: the
 // unrounded packed values (same shape, fp64) or null.
-extern "C" int dx_lr_reduce_pack(void *stream, const double *partial, int64_t nb, int P, int D, int64_t n_items,
-                                 double precision, int64_t *out, double *fout) {
-  if (D <= 0 || P <= D || nb <= 0 || n_items <= 0) return -2;  // rows 0..D must lie inside the slab
-  const int64_t n = n_items * ((int64_t)D + (int64_t)D * (D + 1) / 2);
+extern "C" int dx_lr_reduce_pack_multi(void *stream, const double *partial, int64_t nb, int P, int D, int T,
+                                       int64_t n_items, double precision, int64_t *out, double *fout) {
+  // rows 0..D+T-1 must lie inside the slab
+  if (D <= 0 || T < 1 || T > 64 || P < D + T || nb <= 0 || n_items <= 0) return -2;
+  const int64_t n = n_items * ((int64_t)T * D + (int64_t)D * (D + 1) / 2);
   hipLaunchKernelGGL(lr_reduce_pack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                     partial, nb, P, D, n_items, precision, out, fout);
+                     partial, nb, P, D, T, n_items, precision, out, fout);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) {
     fprintf(stderr, "[drynx_amd native] lr_reduce_pack: %s\n", hipGetErrorString(e));
     return -1;
   }
   return 0;
+}
+
+// One label column: [level 1 (row D), upper triangle], D + D(D+1)/2 values.
+extern "C" int dx_lr_reduce_pack(void *stream, const double *partial, int64_t nb, int P, int D, int64_t n_items,
+                                 double precision, int64_t *out, double *fout) {
+  return dx_lr_reduce_pack_multi(stream, partial, nb, P, D, 1, n_items, precision, out, fout);
 }
 
 // Querier gradient descent for k = 2 (FindMinimumWeights, reference

@@ -76,7 +76,8 @@ def load_dp_file(path: str, op, device="cpu"):
     if op.NameOp == "logistic regression":
         from .logistic_regression import load_csv_dataset
 
-        X, y = load_csv_dataset(path)
+        # a query with T > 1 targets reads label_0,..,label_{T-1},f1,..,fd -> y int64 [n, T]
+        X, y = load_csv_dataset(path, targets=max(1, int(op.LRParameters.NbrTargets or 0)))
         d = int(op.LRParameters.NbrFeatures)
         if X.shape[1] != d:
             raise ValueError(f"{path}: {X.shape[1]} features per record, the query has {d}")

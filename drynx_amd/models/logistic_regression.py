@@ -103,12 +103,25 @@ def augment(X: torch.Tensor) -> torch.Tensor:
     return torch.cat([torch.ones((X.shape[0], 1), dtype=X.dtype, device=X.device), X], dim=1)
 
 
-def n_coeffs(d: int, k: int, packing: int = 0) -> int:
+def n_coeffs(d: int, k: int, packing: int = 0, targets: int = 1) -> int:
     """Values a DP sends: cartesian sum_j (d+1)^(j+1), or with distinct packing
-    (1, k <= 2) D + D(D+1)/2 with D = d + 1."""
-    if packing == 0:
-        return sum((d + 1) ** (j + 1) for j in range(k))
-    return lr_nbr_outputs(d, k, packing)
+    (1, k <= 2) D + D(D+1)/2 with D = d + 1; with T > 1 targets (k <= 2) T
+    level-1 vectors and one level 2."""
+    return lr_nbr_outputs(d, k, packing, targets)
+
+
+def n_targets(params) -> int:
+    """Label columns of a query: NbrTargets 0 and 1 are the single-label query."""
+    return max(1, int(getattr(params, "NbrTargets", 0) or 0))
+
+
+def _label_columns(y: torch.Tensor, T: int) -> list:
+    """The T label columns of ``y`` ([N] or [N, 1] for T = 1, [N, T] beyond)."""
+    if y.dim() == 1 and T == 1:
+        return [y]
+    if y.dim() != 2 or y.shape[1] != T:
+        raise ValueError(f"labels of shape {tuple(y.shape)} for a query with {T} target(s)")
+    return [y[:, t] for t in range(T)]
 
 
 # ----------------------------------------------------------------------------- distinct-coefficient packing
@@ -145,10 +158,11 @@ def pack(vals, d: int, k: int):
     if k != 2:
         raise ValueError("distinct packing is defined for K <= 2 only")
     idx = _triu_flat(D)
+    n1 = (vals.shape[-1] if isinstance(vals, torch.Tensor) else len(vals)) - D * D  # T*D level-1 values
     if isinstance(vals, torch.Tensor):
-        return torch.cat([vals[..., :D], vals[..., D:].index_select(-1, idx.to(vals.device))], -1)
+        return torch.cat([vals[..., :n1], vals[..., n1:].index_select(-1, idx.to(vals.device))], -1)
     vals = list(vals)
-    return vals[:D] + [vals[D + e] for e in idx.tolist()]
+    return vals[:n1] + [vals[n1 + e] for e in idx.tolist()]
 
 
 # ----------------------------------------------------------------------------- approximation coefficients
@@ -157,7 +171,17 @@ def approx_coefficients(Xa: torch.Tensor, y: torch.Tensor, k: int) -> list:
 
     Xa: [N, d+1] standardised+augmented float64; y: [N] in {0,1}.
     Level 1: sum_i (2y_i-1) x_i ; level j: sum_i ypart_j(y_i) * x_i^{(x)j}
-    flattened in cartesian (row-major) order."""
+    flattened in cartesian (row-major) order.
+    y: [N, T], T > 1 (k <= 2): level 1 is the T single-label vectors
+    concatenated (each computed as for y[:, t] alone, so the values are the
+    single-label ones), level 2 the one matrix they share (weight -1)."""
+    if y.dim() == 2:
+        cols = _label_columns(y, y.shape[1])
+        if len(cols) > 1 and k > 2:
+            raise ValueError("several targets share level 2 only: K <= 2")
+        per = [approx_coefficients(Xa, c, k) for c in cols[:1]]
+        per += [approx_coefficients(Xa, c, 1) for c in cols[1:]]
+        return [torch.cat([lv[0] for lv in per])] + per[0][1:]
     y = y.to(torch.float64)
     out = [Xa.T @ (2 * y - 1)]
     for j in range(2, k + 1):
@@ -219,23 +243,46 @@ def encode_coefficients_int_many(Xs: list, ys: list, params: LogisticRegressionP
     d = Xs[0].shape[1] if Xs[0] is not None and Xs[0].dim() == 2 else -1
     if d < 1 or any(X is None or not X.is_cuda or X.dim() != 2 or X.shape[1] != d or len(X) == 0 for X in Xs):
         return None
+    T = n_targets(params)
+    D = d + 1
+    ys = [_label_matrix(y, T) for y in ys]
     if params.Packing == 1:
         # distinct layout: the upper launch plan per DP, then one reduce + pack + round launch
         packed = nt.lr_encode_packed_many([X.to(torch.float64) for X in Xs], ys, params.Means,
                                           params.StandardDeviations, 0.0, -1.0, params.PrecisionApproxCoefficients)
-        return packed[:, :d + 1] if params.K == 1 else packed
+        return packed[:, :T * D] if params.K == 1 else packed
     tot = nt.lr_encode_many([X.to(torch.float64).contiguous() for X in Xs], ys, params.Means,
                             params.StandardDeviations, 0.0, -1.0)
-    D = d + 1
-    lv = tot[:, D, :D] if params.K == 1 else torch.cat([tot[:, D, :D], tot[:, :D, :D].reshape(len(Xs), -1)], 1)
+    lv = tot[:, D, :D] if T == 1 else tot[:, D:D + T, :D].reshape(len(Xs), -1)  # target-major level 1
+    if params.K == 2:
+        lv = torch.cat([lv, tot[:, :D, :D].reshape(len(Xs), -1)], 1)
     return round_precision(lv, params.PrecisionApproxCoefficients)
+
+
+def _label_matrix(y: torch.Tensor, T: int) -> torch.Tensor:
+    """Labels as the fused encoder takes them: [N] for one target, [N, T] for several."""
+    if T == 1:
+        return _label_columns(y, 1)[0]
+    _label_columns(y, T)  # shape check
+    return y
 
 
 def encode_coefficients_int(X: torch.Tensor, y: torch.Tensor, params: LogisticRegressionParameters) -> torch.Tensor:
     """The packed int64 vector the DP encrypts (before encryption)."""
     X = X.to(torch.float64)
+    T = n_targets(params)
+    if T > 1 and params.K > 2:
+        raise ValueError("several targets share level 2 only: K <= 2")
+    y = _label_matrix(y, T)
     if params.Packing == 1:
         return _encode_coefficients_int_packed(X, y, params)
+    if X.is_cuda and T > 1:
+        m, s = (params.Means, params.StandardDeviations) if params.Means and params.StandardDeviations \
+            else compute_means_sds(X)
+        tot = nt.lr_encode_many([X.contiguous()], [y], m, s, 0.0, -1.0)[0]
+        D = X.shape[1] + 1
+        levels = [tot[D:D + T, :D].reshape(-1)] + ([tot[:D, :D].reshape(-1)] if params.K == 2 else [])
+        return torch.cat([round_precision(lv, params.PrecisionApproxCoefficients) for lv in levels])
     if X.is_cuda and params.K <= 2:
         # one fused pass over the records: standardise + augment + level 1 + level 2 (dx_lr_encode)
         if params.Means and params.StandardDeviations:
@@ -267,7 +314,7 @@ def _encode_coefficients_int_packed(X: torch.Tensor, y: torch.Tensor, params) ->
         else:
             m, s = compute_means_sds(X)
         packed = nt.lr_encode_packed_many([X], [y], m, s, 0.0, -1.0, params.PrecisionApproxCoefficients)[0]
-        return packed[:d + 1] if params.K == 1 else packed
+        return packed[:n_targets(params) * (d + 1)] if params.K == 1 else packed
     # host: the cartesian levels as for Packing = 0, then the upper triangle
     if params.Means and params.StandardDeviations:
         Xs = standardise_with(X, params.Means, params.StandardDeviations)
@@ -283,7 +330,7 @@ def encode_logistic_regression(X, y, params: LogisticRegressionParameters, pk: e
     from ..ops.encoding import _encrypt_with_proofs
 
     d = params.NbrFeatures
-    n = n_coeffs(d, params.K, params.Packing)
+    n = n_coeffs(d, params.K, params.Packing, params.NbrTargets)
     if X is None or len(X) == 0:
         vals = [0] * n
     else:
@@ -303,10 +350,19 @@ def mirror_upper(upper: torch.Tensor, D: int) -> torch.Tensor:
     return (A2 + torch.triu(A2, 1).T).reshape(-1)
 
 
-def unpack(vals, d: int, k: int, packing: int = 0) -> list:
+def unpack(vals, d: int, k: int, packing: int = 0, targets: int = 1) -> list:
     """Per-level float64 tensors in the cartesian layout.  ``packing`` 1: the
     D(D+1)/2 distinct level-2 values are mirrored into the symmetric [D, D]
-    matrix (on the host), so the descent below is the same for both layouts."""
+    matrix (on the host), so the descent below is the same for both layouts.
+    ``targets`` T > 1 (k <= 2): [the T level-1 vectors as one [T, D] tensor]
+    and, for k = 2, the one level-2 matrix they share."""
+    if targets > 1:
+        if k > 2:
+            raise ValueError("several targets share level 2 only: K <= 2")
+        D = d + 1
+        vals = list(vals)
+        shared = unpack(vals[(targets - 1) * D:], d, k, packing)  # the last target's level 1, then level 2
+        return [torch.tensor(vals[:targets * D], dtype=torch.float64).reshape(targets, D)] + shared[1:]
     if packing == 1:
         if k > 2:
             raise ValueError("distinct packing is defined for K <= 2 only")
@@ -427,9 +483,22 @@ def find_minimum_weights_with_encryption(encrypted: list, secret: int, initial_w
 def decode_logistic_regression_values(vals, params: LogisticRegressionParameters) -> list:
     with timers.timed("GradientDescent", sync=False):
         approx = [a / params.PrecisionApproxCoefficients
-                  for a in unpack(vals, params.NbrFeatures, params.K, params.Packing)]
-        init = params.InitialWeights or [0.0] * (params.NbrFeatures + 1)
-        return find_minimum_weights(approx, init, params.NbrRecords, params.Lambda, params.Step, params.MaxIterations)
+                  for a in unpack(vals, params.NbrFeatures, params.K, params.Packing, n_targets(params))]
+        D = params.NbrFeatures + 1
+        init = list(params.InitialWeights or [0.0] * D)
+        T = n_targets(params)
+        if T == 1:
+            return find_minimum_weights(approx, init, params.NbrRecords, params.Lambda, params.Step,
+                                        params.MaxIterations)
+        # one descent per target against the shared level 2; the weights target-major in one flat list
+        if len(init) not in (D, T * D):
+            raise ValueError(f"{len(init)} initial weights for {T} targets of {D} weights")
+        out = []
+        for t in range(T):
+            w0 = init if len(init) == D else init[t * D:(t + 1) * D]
+            out += list(find_minimum_weights([approx[0][t]] + approx[1:], w0, params.NbrRecords, params.Lambda,
+                                             params.Step, params.MaxIterations))
+        return out
 
 
 # ----------------------------------------------------------------------------- prediction & metrics
@@ -440,6 +509,26 @@ def predict(X: torch.Tensor, weights, means=None, sds=None) -> torch.Tensor:
     Xa = augment(X)
     w = torch.as_tensor(weights, dtype=torch.float64, device=X.device)
     return torch.sigmoid(Xa @ w)
+
+
+def split_targets(weights, T: int) -> list:
+    """The flat target-major weight list of a T-target query -> T lists of d + 1 weights."""
+    w = list(weights)
+    T = max(1, int(T))
+    if len(w) % T:
+        raise ValueError(f"{len(w)} weights do not split into {T} targets")
+    D = len(w) // T
+    return [w[t * D:(t + 1) * D] for t in range(T)]
+
+
+def predict_targets(X: torch.Tensor, weights, T: int, means=None, sds=None) -> torch.Tensor:
+    """[n, T] probabilities: column t is ``predict`` with target t's weights."""
+    return torch.stack([predict(X, w, means, sds) for w in split_targets(weights, T)], dim=1)
+
+
+def predict_class(X: torch.Tensor, weights, T: int, means=None, sds=None) -> torch.Tensor:
+    """One-vs-rest: the target with the largest probability per record -> [n] int64."""
+    return predict_targets(X, weights, T, means, sds).argmax(dim=1)
 
 
 def predict_in_clear(x, weights) -> float:
@@ -543,10 +632,17 @@ def partition_for_dp(X: torch.Tensor, y: torch.Tensor, dp_index: int, n_dps: int
     return X[s:e], y[s:e]
 
 
-def load_csv_dataset(path: str, label_col: int = 0, drop_cols=()):
-    """Dataset loader: CSV with the label in column 0 (logistic_regression.go GetDataForDataProvider)."""
+def load_csv_dataset(path: str, label_col: int = 0, drop_cols=(), targets: int = 1):
+    """Dataset loader: CSV with the label in column 0 (logistic_regression.go GetDataForDataProvider).
+    ``targets`` T > 1: ``label_0,..,label_{T-1},f1,..,fd`` per line -> (X [n, d], y [n, T])."""
     import numpy as np
 
+    if targets > 1:
+        data = np.loadtxt(path, delimiter=",", ndmin=2)
+        if label_col != 0 or data.shape[1] <= targets:
+            raise ValueError(f"{path}: {targets} label columns lead each record, then the features")
+        keep = [c for c in range(targets, data.shape[1]) if c not in drop_cols]
+        return torch.tensor(data[:, keep], dtype=torch.float64), torch.tensor(data[:, :targets], dtype=torch.int64)
     data = np.loadtxt(path, delimiter=",")
     keep = [c for c in range(data.shape[1]) if c != label_col and c not in drop_cols]
     X = torch.tensor(data[:, keep], dtype=torch.float64)

@@ -103,6 +103,8 @@ _SIGS = {
     "dx_lr_reduce": [_P, _P, _L, _L, _L, _P],
     "dx_lr_encode_upper": [_P, _P, _L, _L, _I, _P, _P, _P, ctypes.c_double, ctypes.c_double, _P, _I, _I],
     "dx_lr_reduce_pack": [_P, _P, _L, _I, _I, _L, ctypes.c_double, _P, _P],
+    "dx_lr_encode_multi": [_P, _P, _L, _L, _I, _P, _P, _P, _L, _I, ctypes.c_double, _P, _I, _I, _I],
+    "dx_lr_reduce_pack_multi": [_P, _P, _L, _I, _I, _I, _L, ctypes.c_double, _P, _P],
     "dx_g1_mul_glv256": [_P, _P, _P, _P, _P, _L, _I, _I, _I],
     "dx_glv_split": [_I, _P, _P, _P, _L],
     "dx_gt_t2_compress": [_I, _P, _P, _P, _P, _L],
@@ -1230,18 +1232,34 @@ def _lr_blocks(N: int) -> int:
     return int(max(1, min(1024, (steps + 15) // 16)))
 
 
+def _lr_targets(ys: list) -> int:
+    """Label columns T of a batch: every entry [N] (or [N, 1]) -> 1, every entry [N, T] -> T."""
+    ts = {1 if y.dim() == 1 else int(y.shape[1]) for y in ys if y.dim() in (1, 2)}
+    if len(ts) != 1 or any(y.dim() not in (1, 2) for y in ys):
+        raise ValueError("lr_encode: the labels of a batch are all [N] or all [N, T] with one T")
+    return ts.pop()
+
+
 def _lr_launch_many(Xs: list, ys: list, mean, sd, wa: float, wb: float, upper: bool):
     """One encoder call per DP into one [n, nb, P, P] partial slab (nb = the
     longest DP's record blocks) -> (slab, D).  ``upper``: the packed layout's
     launch plan (dx_lr_encode_upper), which leaves the tile-blocks strictly
-    below the diagonal unwritten."""
+    below the diagonal unwritten.  Labels [N] (or [N, 1]): the single-label
+    kernels, level 1 in row D.  Labels [N, T], T >= 2 (rows may be strided):
+    dx_lr_encode_multi, level 1 of target t in row D + t, level-2 weight the
+    constant ``wb`` (``wa`` must be 0: no label-dependent level-2 weight)."""
     X0 = Xs[0]
     dev = X0.device
     dx = X0.shape[1]
     if dx < 1:
         raise ValueError("lr_encode needs at least one feature")
     D = dx + 1
-    P = _lr_padded(D + 1)
+    T = _lr_targets(ys)
+    if T < 1:
+        raise ValueError("lr_encode needs at least one label column")
+    if T > 1 and float(wa) != 0.0:
+        raise ValueError("lr_encode: several label columns share one level 2, so its weight cannot depend on a label")
+    P = _lr_padded(D + T)
     mean = torch.as_tensor(mean, dtype=torch.float64).to(dev).contiguous()
     sd = torch.as_tensor(sd, dtype=torch.float64).to(dev).contiguous()
     assert mean.numel() == dx and sd.numel() == dx
@@ -1250,27 +1268,42 @@ def _lr_launch_many(Xs: list, ys: list, mean, sd, wa: float, wb: float, upper: b
     # Invariant: the slab is torch.empty only when every record block of every
     # DP is written AND every element the reducer will read is written;
     # otherwise it is zero-filled, so that what is read but unwritten adds
-    # nothing.  A shorter DP's trailing blocks are never written.  The full
-    # reducer reads all of [P, P], of which a wide launch leaves the column
-    # tiles past D unwritten.  The packed reducer reads only (i, j), i <= j < D,
-    # and row D, all of which the upper plan writes: what that plan skips
-    # (below the diagonal) and the padding columns are never read, so they may
-    # stay uninitialised.
+    # nothing.  A shorter DP's trailing blocks are never written.  Written are
+    # the live tiles: all of [48, 48] when P = 48, else row tiles 0..P/16-1
+    # (rows 0..D+T-1: every row tile holds a live row) by column tiles
+    # 0..ceil(D/16)-1, minus, in the upper plan, the tile-blocks strictly below
+    # the diagonal of tile-block rows that hold no row >= D.  The full reducer
+    # reads all of [P, P], of which a wide launch leaves the column tiles past
+    # D unwritten: with T label columns P grows with D + T while the column
+    # tiles stay ceil(D/16), so this holds only while the two counts agree.
+    # The packed reducer reads only (i, j), i <= j < D, which lies on or above
+    # the diagonal, and rows D..D+T-1 at columns < D, whose tile-block rows the
+    # upper plan launches whole: all written.  What that plan skips and the
+    # padding columns are never read, so they may stay uninitialised.
     full = all(b == nb for b in nbs) and (upper or P == 48 or (D + 15) // 16 == P // 16)
     alloc = torch.empty if full else torch.zeros
     partial = alloc((len(Xs), nb, P, P), dtype=torch.float64, device=dev)
     _, s = _ctx(X0)
     keep = []
-    name = "dx_lr_encode_upper" if upper else "dx_lr_encode"
+    name = "dx_lr_encode_multi" if T > 1 else ("dx_lr_encode_upper" if upper else "dx_lr_encode")
     for i, (X, y) in enumerate(zip(Xs, ys)):
         assert X.is_cuda and X.dtype == torch.float64 and X.dim() == 2 and X.stride(1) == 1 and X.shape[1] == dx
         N = X.shape[0]
-        y = y.to(device=dev, dtype=torch.float64).contiguous()
-        assert y.numel() == N
-        keep.append(y)
+        y = y.to(device=dev, dtype=torch.float64)
         # rows may be strided (a column slice of a wider matrix): the kernel takes the row stride
-        rc = _raw_call(name, s, ctypes.c_void_p(X.data_ptr()), X.stride(0), N, dx, _ptr(mean), _ptr(sd),
-                       _ptr(y), float(wa), float(wb), _ptr(partial[i]), nbs[i], P)
+        if T == 1:
+            y = y.reshape(-1).contiguous()
+            assert y.numel() == N
+            rc = _raw_call(name, s, ctypes.c_void_p(X.data_ptr()), X.stride(0), N, dx, _ptr(mean), _ptr(sd),
+                           _ptr(y), float(wa), float(wb), _ptr(partial[i]), nbs[i], P)
+        else:
+            if y.stride(1) != 1 or (N > 1 and y.stride(0) < T):
+                y = y.contiguous()
+            assert y.shape == (N, T)
+            rc = _raw_call(name, s, ctypes.c_void_p(X.data_ptr()), X.stride(0), N, dx, _ptr(mean), _ptr(sd),
+                           ctypes.c_void_p(y.data_ptr()), y.stride(0) if N > 1 else T, T, float(wb), _ptr(partial[i]),
+                           nbs[i], P, 1 if upper else 0)
+        keep.append(y)
         if rc != 0:
             raise RuntimeError(f"{name} failed rc={rc}")
     return partial, D
@@ -1296,35 +1329,43 @@ def lr_encode_many(Xs: list, ys: list, mean, sd, wa: float, wb: float) -> torch.
     launch (dx_lr_reduce, fixed summation order: a DP's totals are the same
     bits alone or batched) -> [n, P, P] totals with level 2 in [:D, :D] and
     level 1 in row D (D = features + 1; P = 48 up to 46 features, the
-    16-padded D + 1 beyond; entries outside those are padding)."""
+    16-padded D + 1 beyond; entries outside those are padding).  Labels
+    [N, T], T >= 2: level 1 of target t in row D + t, one shared level 2 with
+    the constant weight ``wb``, P = 48 while D + T <= 48 and the 16-padded
+    D + T beyond."""
     partial, _ = _lr_launch_many(Xs, ys, mean, sd, wa, wb, False)
     return lr_reduce(partial)
 
 
-def lr_packed_len(D: int) -> int:
-    """Length of the distinct-coefficient vector: level 1 (D) + the upper triangle of level 2."""
-    return D + D * (D + 1) // 2
+def lr_packed_len(D: int, T: int = 1) -> int:
+    """Length of the distinct-coefficient vector: level 1 (D per label column) + the upper triangle of level 2."""
+    return T * D + D * (D + 1) // 2
 
 
-def lr_reduce_pack(partial: torch.Tensor, D: int, precision: float, floats: bool = False):
+def lr_reduce_pack(partial: torch.Tensor, D: int, precision: float, floats: bool = False, T: int = 1):
     """Block partials [n, nb, P, P] (or [nb, P, P]: one item) -> the packed
     int64 vectors [n, D + D(D+1)/2] in ONE launch (dx_lr_reduce_pack): level 1
     from row D, then level 2's upper triangle row-major, summed over the
     blocks in dx_lr_reduce's order, times ``precision``, rounded half away from
     zero.  Reads only (i, j), i <= j < D, and row D of each block.
-    ``floats``: also return the unrounded packed fp64 values."""
+    ``floats``: also return the unrounded packed fp64 values.  ``T`` label
+    columns: [n, T*D + D(D+1)/2], level 1 of target t from row D + t."""
     if partial.dim() == 3:
         partial = partial[None]
     assert partial.is_cuda and partial.dtype == torch.float64 and partial.dim() == 4 and partial.is_contiguous()
     n, nb, P, P2 = partial.shape
-    D = int(D)
-    if not (P == P2 and 1 <= D < P and n >= 1 and nb >= 1):
-        raise ValueError(f"lr_reduce_pack: slab {tuple(partial.shape)} does not hold rows 0..{D}")
+    D, T = int(D), int(T)
+    if not (P == P2 and 1 <= D and 1 <= T and D + T <= P and n >= 1 and nb >= 1):
+        raise ValueError(f"lr_reduce_pack: slab {tuple(partial.shape)} does not hold rows 0..{D + T - 1}")
     dev = partial.device
-    out = torch.empty((n, lr_packed_len(D)), dtype=torch.int64, device=dev)
-    fout = torch.empty((n, lr_packed_len(D)), dtype=torch.float64, device=dev) if floats else None
+    out = torch.empty((n, lr_packed_len(D, T)), dtype=torch.int64, device=dev)
+    fout = torch.empty((n, lr_packed_len(D, T)), dtype=torch.float64, device=dev) if floats else None
     _, s = _ctx(partial)
-    rc = _raw_call("dx_lr_reduce_pack", s, _ptr(partial), nb, P, D, n, float(precision), _ptr(out), _ptr(fout))
+    if T == 1:
+        rc = _raw_call("dx_lr_reduce_pack", s, _ptr(partial), nb, P, D, n, float(precision), _ptr(out), _ptr(fout))
+    else:
+        rc = _raw_call("dx_lr_reduce_pack_multi", s, _ptr(partial), nb, P, D, T, n, float(precision), _ptr(out),
+                       _ptr(fout))
     if rc != 0:
         raise RuntimeError(f"dx_lr_reduce_pack failed rc={rc}")
     return (out, fout) if floats else out
@@ -1335,9 +1376,11 @@ def lr_encode_packed_many(Xs: list, ys: list, mean, sd, wa: float, wb: float, pr
     int64 [n, D + D(D+1)/2] (``floats``: and the unrounded fp64 values): per DP
     the encoder's upper launch plan, then ONE reduce + pack + round launch for
     the batch.  Rows may be strided, any d >= 1, DPs of unequal length.  Entry
-    (i, j), i <= j, is the same bits as ``lr_encode_many``'s value there."""
+    (i, j), i <= j, is the same bits as ``lr_encode_many``'s value there.
+    Labels [N, T], T >= 2: int64 [n, T*D + D(D+1)/2], the T level-1 vectors
+    (target-major), then the one shared upper triangle."""
     partial, D = _lr_launch_many(Xs, ys, mean, sd, wa, wb, True)
-    return lr_reduce_pack(partial, D, precision, floats)
+    return lr_reduce_pack(partial, D, precision, floats, _lr_targets(ys))
 
 
 # ----------------------------------------------------------------------------- range proofs (K15/K16)

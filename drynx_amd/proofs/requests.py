@@ -500,6 +500,14 @@ class VerifierCache:
             self._sig[key] = bn.publish(rp.SigMaterial(sigs, device))
         return self._sig[key]
 
+    def drop_signature_tables(self, device) -> None:
+        """Forget every signature set (their prover and verifier tables go back
+        to the allocator once the device has drained): for a process that
+        alternates between sets too large to be resident together."""
+        if torch.device(device).type == "cuda":
+            torch.cuda.synchronize(device)
+        self._sig.clear()
+
 
 def _range_table(sq):
     """The query's Ranges as int64 columns (u, l, offset) plus a validity

@@ -40,7 +40,7 @@ def expected_n_out(sq) -> int | None:
     cf = max(1, q.CuttingFactor or 1)
     if op.NameOp == "logistic regression":
         p = op.LRParameters
-        return None if p is None else lr_nbr_outputs(p.NbrFeatures, p.K, p.Packing) * cf
+        return None if p is None else lr_nbr_outputs(p.NbrFeatures, p.K, p.Packing, p.NbrTargets) * cf
     return (op.NbrOutput // cf) * cf if op.NbrOutput > 0 else None
 
 
@@ -62,13 +62,16 @@ def generate_fake_data(op, nbr_rows: int, lo: int, hi: int, device, gen: torch.G
 def generate_lr_data(params, device, gen: torch.Generator):
     """Synthetic LR records (data_collection_protocol.go:226-241 dummy rows):
     features uniform in [0, 4) as float64, labels uniform {0,1}; generated on
-    the DP's device so 1e6-record DPs never touch the host."""
+    the DP's device so 1e6-record DPs never touch the host.  A query with
+    T > 1 label columns draws the labels as [n, T] (the single-label draws are
+    unchanged)."""
     n, m = int(params.NbrRecords), int(params.NbrFeatures)
     g = torch.Generator(device=device) if torch.device(device).type == "cuda" else gen
     if torch.device(device).type == "cuda":
         g.manual_seed(int(gen.initial_seed()))
     X = torch.randint(0, 4, (n, m), generator=g, device=device).to(torch.float64)
-    y = torch.randint(0, 2, (n,), generator=g, device=device)
+    t = int(getattr(params, "NbrTargets", 0) or 0)
+    y = torch.randint(0, 2, (n, t) if t > 1 else (n,), generator=g, device=device)
     return X, y
 
 
@@ -187,8 +190,8 @@ def _lr_values(ctx, sq, dps: list, device) -> torch.Tensor:
     out = []
     for X, y in data:
         if X is None or len(X) == 0:
-            out.append(torch.zeros(n_coeffs(params.NbrFeatures, params.K, params.Packing), dtype=torch.int64,
-                                   device=device))
+            out.append(torch.zeros(n_coeffs(params.NbrFeatures, params.K, params.Packing, params.NbrTargets),
+                                   dtype=torch.int64, device=device))
         else:
             out.append(encode_coefficients_int(torch.as_tensor(X, device=device), torch.as_tensor(y, device=device),
                                                params).to(device))

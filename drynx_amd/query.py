@@ -134,6 +134,12 @@ class LogisticRegressionParameters:
     # cartesian (d+1)^2 values; 1 = distinct: only the upper triangle (i <= j)
     # of the symmetric level-2 matrix, row-major, D(D+1)/2 values (K <= 2).
     Packing: int = 0
+    # extension: label columns.  0 and 1 = the reference's single-label query;
+    # 2..64 = T binary models over the same features in one query: the DPs'
+    # labels are [N, T], level 1 is sent once per target (target-major) and
+    # level 2, whose weight y - y(-1)^2 - 1 = -1 does not depend on the label,
+    # once for all of them (K <= 2).  Travels as SurveyQuery.LRTargets on the wire.
+    NbrTargets: int = 0
 
 
 @dataclass
@@ -350,6 +356,15 @@ def check_parameters(sq: SurveyQuery, diffp: bool) -> bool:
             msg.append("logistic regression packing is neither 0 (cartesian) nor 1 (distinct)")
         elif lrp.Packing == 1 and lrp.K > 2:
             msg.append("distinct packing is defined for K <= 2 only")
+        nt = lrp.NbrTargets
+        if not isinstance(nt, int) or not 0 <= nt <= MAX_LR_TARGETS:
+            msg.append(f"logistic regression targets outside 0..{MAX_LR_TARGETS}")
+        else:
+            if nt > 1 and lrp.K > 2:
+                msg.append("several targets share level 2 only: K <= 2 (level 3's weight depends on the label)")
+            D = lrp.NbrFeatures + 1
+            if len(lrp.InitialWeights or []) not in (0, D, max(1, nt) * D):
+                msg.append("initial weights are neither empty, one vector of d + 1 nor one per target")
     if q.Operation.QueryMin != q.DPDataGen.GenerateDataMin or q.Operation.QueryMax != q.DPDataGen.GenerateDataMax:
         msg.append("min or max are inconsistent at DP and operations")
     for m in msg:
@@ -400,16 +415,27 @@ def choose_operation(name: str, query_min: int, query_max: int, d: int, cutting_
     return op
 
 
-def lr_nbr_outputs(d: int, k: int, packing: int = 0) -> int:
+MAX_LR_TARGETS = 64
+
+
+def lr_nbr_outputs(d: int, k: int, packing: int = 0, targets: int = 1) -> int:
     """getTotalNumberApproxCoefficients (logistic_regression.go:306): sum_j (d+1)^(j+1).
     ``packing`` 1 (extension, k <= 2): level 2 is sent as the D(D+1)/2 distinct
-    entries (i <= j) of the symmetric matrix, D = d + 1."""
+    entries (i <= j) of the symmetric matrix, D = d + 1.  ``targets`` T > 1
+    (extension, k <= 2): T level-1 vectors and ONE level 2, T*D + D^2 or
+    T*D + D(D+1)/2; 0 and 1 are the single-label count."""
+    t = int(targets)
+    if not 0 <= t <= MAX_LR_TARGETS:
+        raise ValueError(f"no {targets} targets")
+    if t > 1 and k > 2:
+        raise ValueError(f"{targets} targets for k = {k}: level 3 depends on the label")
+    extra = (max(1, t) - 1) * (d + 1)
     if packing == 0:
-        return sum((d + 1) ** (j + 1) for j in range(k))
+        return extra + sum((d + 1) ** (j + 1) for j in range(k))
     if packing != 1 or k > 2:
         raise ValueError(f"no packing {packing} for k = {k}")
     D = d + 1
-    return D if k == 1 else D + D * (D + 1) // 2
+    return extra + (D if k == 1 else D + D * (D + 1) // 2)
 
 
 def new_survey_id() -> str:

@@ -59,7 +59,7 @@ def make_survey(client: DrynxClient, cluster, op_name: str, *, query_min=0, quer
     op = choose_operation(op_name, query_min, query_max, d, cutting_factor)
     if op_name == "logistic regression":
         op.LRParameters = lr_params
-        op.NbrOutput = lr_nbr_outputs(lr_params.NbrFeatures, lr_params.K, lr_params.Packing)
+        op.NbrOutput = lr_nbr_outputs(lr_params.NbrFeatures, lr_params.K, lr_params.Packing, lr_params.NbrTargets)
     n_out = op.NbrOutput
     if ranges is not None and (len(ranges) == 0 or not isinstance(ranges[0], (list, tuple))):
         ranges = [list(ranges) for _ in range(n_out)]  # one (u, l[, offset]) for every output

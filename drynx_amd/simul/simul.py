@@ -100,12 +100,14 @@ def run_row(glob: dict, row: dict, comm, device, workdir, netem: str = "sleep"):
     d = int(row.get("NbrInput", 1)) - 1 if op_name == "lin_reg" else 1
     if op_name == "logistic regression":
         n_feat = int(glob.get("NbrFeatures", row.get("NbrInput", 8)))
+        n_tgt = int(row.get("LRTargets", 0))  # optional column (extension): label columns per query
         lr = LogisticRegressionParameters(NbrRecords=int(row.get("NbrRecords", 100)), NbrFeatures=n_feat,
                                           Lambda=1.0, Step=0.012, MaxIterations=int(row.get("MaxIterations", 25)),
                                           InitialWeights=[0.1] * (n_feat + 1), K=2,
                                           PrecisionApproxCoefficients=100.0, Means=[1.5] * n_feat,
                                           StandardDeviations=[1.1] * n_feat,
-                                          Packing=int(row.get("LRPacking", 0)))  # optional column (extension)
+                                          Packing=int(row.get("LRPacking", 0)),  # optional column (extension)
+                                          NbrTargets=n_tgt)
     diffp = None
     if int(row.get("DiffPSize", 0)):
         diffp = QueryDiffP(LapMean=float(row.get("DiffPEpsilon", 0)),
@@ -124,7 +126,7 @@ def run_row(glob: dict, row: dict, comm, device, workdir, netem: str = "sleep"):
             if lr is not None:
                 from ..query import lr_nbr_outputs
 
-                n_out = lr_nbr_outputs(lr.NbrFeatures, lr.K, lr.Packing)
+                n_out = lr_nbr_outputs(lr.NbrFeatures, lr.K, lr.Packing, lr.NbrTargets)
             rg = ranges_for(int(row.get("Ranges", -1)), n_out) if proofs else None
             thr_g, thr_o = float(row.get("ThresholdGeneral", 0)), float(row.get("ThresholdOther", 0))
             obf = bool(row.get("Obfuscation", False))

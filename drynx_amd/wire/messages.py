@@ -71,7 +71,7 @@ def survey_query_to_msg(sq: SurveyQuery) -> dict:
         "Query": {
             "Operation": {"NameOp": op.NameOp, "NbrInput": op.NbrInput, "NbrOutput": op.NbrOutput,
                           "QueryMin": op.QueryMin, "QueryMax": op.QueryMax,
-                          "LRParameters": dict(lr.__dict__)},
+                          "LRParameters": {k: v for k, v in lr.__dict__.items() if k != "NbrTargets"}},
             "Ranges": [list(r) for r in (q.Ranges or [])],
             "Proofs": q.Proofs,
             "Obfuscation": q.Obfuscation,
@@ -93,13 +93,17 @@ def survey_query_to_msg(sq: SurveyQuery) -> dict:
         "KeySwitchingProofThreshold": sq.KeySwitchingProofThreshold,
         "VerificationSharding": sq.VerificationSharding,
         "RangeProofMode": sq.RangeProofMode,
+        "LRTargets": lr.NbrTargets,
     }
 
 
 def survey_query_from_msg(d: dict) -> SurveyQuery:
     q = d["Query"] or {}
     op = q.get("Operation") or {}
-    lr = op.get("LRParameters") or {}
+    lr = dict(op.get("LRParameters") or {})
+    lr.pop("NbrTargets", None)
+    lrp = LogisticRegressionParameters(**lr) if lr else LogisticRegressionParameters()
+    lrp.NbrTargets = int(d.get("LRTargets") or 0)  # absent (a sender without the extension) reads as 0
     ivs = q.get("IVSigs") or {}
     sigs = ivs.get("InputValidationSigs") or []
     return SurveyQuery(
@@ -110,8 +114,7 @@ def survey_query_from_msg(d: dict) -> SurveyQuery:
         ServerToDP={k: [server_identity_from_msg(s) for s in v] for k, v in d["ServerToDP"].items()},
         Query=Query(
             Operation=Operation(op.get("NameOp", ""), op.get("NbrInput", 0), op.get("NbrOutput", 0),
-                                op.get("QueryMin", 0), op.get("QueryMax", 0),
-                                LogisticRegressionParameters(**lr) if lr else LogisticRegressionParameters()),
+                                op.get("QueryMin", 0), op.get("QueryMax", 0), lrp),
             Ranges=[list(r) for r in q.get("Ranges", [])] or None,
             Proofs=q.get("Proofs", 0),
             Obfuscation=q.get("Obfuscation", False),

@@ -65,7 +65,10 @@ SURVEY_QUERY = (("SurveyID", "string"), ("RosterServers", ("msg", ROSTER)), ("Cl
                 ("AggregationProofThreshold", "double"), ("ObfuscationProofThreshold", "double"),
                 ("RangeProofThreshold", "double"), ("KeySwitchingProofThreshold", "double"),
                 # drynx_amd extension (after the reference fields): per-proof VN sharding
-                ("VerificationSharding", "sint"), ("RangeProofMode", "sint"))
+                ("VerificationSharding", "sint"), ("RangeProofMode", "sint"),
+                # drynx_amd extension: label columns of a logistic-regression query
+                # (LRParameters.NbrTargets; here, not in LR_PARAMETERS, whose field numbers are stored in blocks)
+                ("LRTargets", "sint"))
 SURVEY_QUERY_TO_VN = (("SQ", ("msg", SURVEY_QUERY)),)
 SURVEY_QUERY_TO_DP = (("SQ", ("msg", SURVEY_QUERY)), ("Root", ("msg", SERVER_IDENTITY)))
 # VN requests: the reference sends them to the VN's own server; here one entry
