@@ -113,6 +113,9 @@ _SIGS = {
     "dx_gt_t2_decompress": [_I, _P, _P, _P, _L],
     "dx_gt_slice_prod": [_I, _P, _P, _P, _P, _P, _P, _L],
     "dx_gt_chunk_weight": [_I, _P, _P, _P, _P, _P, _P, _P, _L],
+    "dx_gt_beta_rows": [_I, _P, _P, _P, _L, _L],
+    "dx_gt_beta_slice_prod": [_I, _P, _P, _P, _P, _P, _P, _L],
+    "dx_gt_pi": [_I, _P, _P, _P, _L],
     "dx_g1_mul_glv": [_P, _P, _P, _P, _P, _L, _I],
     "dx_rp_u_joint_split": [_I, _P, _P, _P, _P, _L, _I, _I, _L, _I, _P, _P],
     "dx_bucket_bounds": [_I, _P, _P, _L, _L, _P, _P],
@@ -1590,6 +1593,31 @@ def gt_frob8(a: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
     return out
 
 
+def gt_beta_rows(a: torch.Tensor, rows_per_inv: int | None = None) -> torch.Tensor:
+    """Unitary GT elements a [m, 96] -> beta2 [2m, 48]: row i the torus image
+    (1 + g) / h of a_i = g + h w (the limbs ``gt_t2_compress`` writes), row
+    m + i the image of frob^8(a_i); a row with h = 0 (a_i = 1) is all zero in
+    both halves, the skip mark of ``gt_beta_slice_prod``
+    (csrc/kernels/dx_me_torus.hip).  ``rows_per_inv`` rows share one Fp6
+    inversion (default: up to 8, no more than keeps two waves per SIMD)."""
+    m = _rows(a, 96)
+    if rows_per_inv is None:
+        rows_per_inv = 8 if a.device.type != "cuda" else max(1, min(8, m // (1024 * 64 * 2)))
+    out = torch.empty((2 * m, 48), dtype=torch.int32, device=a.device)
+    g, s = _ctx(a)
+    _call("dx_gt_beta_rows", g, s, _ptr(a.contiguous()), _ptr(out), m, int(rows_per_inv))
+    return out
+
+
+def gt_pi(y: torch.Tensor) -> torch.Tensor:
+    """Numerators y [n, 96] (non-zero Fp12 values) -> pi(y) = y / conj(y), the
+    canonical unitary values (csrc/bn254/gt_torus.h)."""
+    out = torch.empty_like(y)
+    g, s = _ctx(y)
+    _call("dx_gt_pi", g, s, _ptr(y.contiguous()), _ptr(out), _rows(y, 96))
+    return out
+
+
 def rp_fold_coeffs(V_aff: torch.Tensor) -> torch.Tensor:
     """The raw line coefficients (c0, c1, c3) of every V's Miller loop (no P)
     -> flat int32 image [steps * 12 * m * 4]; several verifiers folding the
@@ -1742,5 +1770,6 @@ def _gt_prod_level(x: torch.Tensor, ch: int) -> torch.Tensor:
 # the verifier's multi-scalar products (bucket plans over the ops above): last, msm.py imports from this module
 from .msm import (G2_CHUNK, capture_keep, check_overflow, g1_msm, g1_msm_device, g1_msm_finish,  # noqa: E402,F401
                   g1_msm_grouped, g1_msm_launch, g1_msm_plan, g1_slice_sum, g2_chunk_weight, g2_msm_device,
-                  g2_msm_finish, g2_msm_launch, g2_msm_run, g2_slice_sum, gt_chunk_weight, gt_slice_prod, me_window,
-                  multi_exp_device, multi_exp_grouped, multi_exp_grouped_finish, multi_exp_plan, rp_msm_uv)
+                  g2_msm_finish, g2_msm_launch, g2_msm_run, g2_slice_sum, gt_beta_slice_prod, gt_chunk_weight,
+                  gt_slice_prod, me_window, multi_exp_device, multi_exp_grouped, multi_exp_grouped_finish,
+                  multi_exp_plan, rp_msm_uv)

@@ -24,9 +24,12 @@ import numpy as np
 import torch
 
 from . import (_call, _ctx, _gt_prod_level, _pow2_scalar, _ptr, _raw_call, _rows, _upload, g1_mul, gt_mul, gt_one,
-               gt_pow, gt_prod)
+               gt_pi, gt_pow, gt_prod)
 
 _ME_SLICE = 8      # entries per thread in each segmented-product pass
+# entries per lane pair in the first pass over torus images (gt_beta_slice_prod): the first factor of a
+# slice is free and a step costs two Fp6 products, so longer slices pay (profiles/me_torus/README.md)
+_ME_TORUS_SLICE = 32
 G2_CHUNK = 32      # digit range of one running-sum chunk of Pippenger buckets
 
 
@@ -40,6 +43,21 @@ def gt_slice_prod(src: torch.Tensor, idx, start: torch.Tensor, length: torch.Ten
     out = torch.empty((n, 96), dtype=torch.int32, device=src.device)
     g, s = _ctx(src, idx, start, length)
     _call("dx_gt_slice_prod", g, s, _ptr(src), _ptr(idx), _ptr(start), _ptr(length), _ptr(out), n)
+    return out
+
+
+def gt_beta_slice_prod(beta: torch.Tensor, idx, start: torch.Tensor, length: torch.Tensor) -> torch.Tensor:
+    """out[s] = a numerator (gt_torus.h) of prod_k pi(beta[idx[start[s] + k]] + w)
+    (or beta[start[s] + k]), k < length[s], over torus images beta [., 48]: the
+    first row of a slice is free, every further one costs two Fp6 products.
+    All-zero rows are skipped; an empty slice gives 1.  ``gt_pi`` of the result
+    is ``gt_slice_prod`` over the elements the rows are images of."""
+    n = start.numel()
+    assert beta.shape[-1] == 48 and (idx is None or idx.dtype == torch.int64)
+    assert start.dtype == torch.int64 and length.dtype == torch.int32
+    out = torch.empty((n, 96), dtype=torch.int32, device=beta.device)
+    g, s = _ctx(beta, idx, start, length)
+    _call("dx_gt_beta_slice_prod", g, s, _ptr(beta), _ptr(idx), _ptr(start), _ptr(length), _ptr(out), n)
     return out
 
 
@@ -99,8 +117,12 @@ def g2_chunk_weight(B_jac: torch.Tensor, d: torch.Tensor, start: torch.Tensor, l
 # the level before.  The groups' index types and row periods stay in here.
 def _gt_ops(a: torch.Tensor, items: torch.Tensor, item_split: tuple | None = None):
     """Entry i reads a[i % n] (n = rows of a); with ``item_split`` = (s, q)
-    entry i >= s reads a[(i - s) % q].  The kernel takes int64 premapped rows."""
+    entry i >= s reads a[(i - s) % q].  The kernel takes int64 premapped rows.
+    ``a`` is [n, 96] Fp12 rows or [n, 48] torus images (``gt_beta_rows``): with
+    images the first pass leaves numerators, which are ordinary Fp12 values,
+    so every later pass is the same generic product."""
     n = a.shape[0]
+    first = gt_beta_slice_prod if a.shape[-1] == 48 else gt_slice_prod
     it = items.to(torch.int64)
     if item_split is not None:
         sp, q = item_split
@@ -108,7 +130,7 @@ def _gt_ops(a: torch.Tensor, items: torch.Tensor, item_split: tuple | None = Non
     else:
         it = it % n
     it = it.contiguous()
-    return (lambda st, ln: gt_slice_prod(a, it, st, ln)), (lambda cur, st, ln: gt_slice_prod(cur, None, st, ln))
+    return (lambda st, ln: first(a, it, st, ln)), (lambda cur, st, ln: gt_slice_prod(cur, None, st, ln))
 
 
 def _g1_ops(P_jac: torch.Tensor, items: torch.Tensor):
@@ -504,17 +526,24 @@ def multi_exp_grouped(a: torch.Tensor, k: torch.Tensor, group, n_groups: int, W:
 
 
 def multi_exp_device(a: torch.Tensor, k: torch.Tensor, group, groups: tuple, W: int | None = None,
-                     c: int | None = None, item_split: tuple | None = None) -> dict:
+                     c: int | None = None, item_split: tuple | None = None, first_slice: int | None = None) -> dict:
     """``multi_exp_grouped`` with a device-resident plan (no host sync):
     ``groups`` = ((entries, exponent bits), ...) per group (window from
     ``me_window`` unless given).  -> the handle of ``multi_exp_grouped_finish``.
     ``item_split`` = (s, q): entry i < s uses a[i % n], entry i >= s uses
-    a[(i - s) % q] (two exponent blocks over different row periods)."""
+    a[(i - s) % q] (two exponent blocks over different row periods).
+    ``a`` [n, 48]: torus images of the rows (``gt_beta_rows``) -- the first
+    pass then runs on numerators (``gt_beta_slice_prod``, ``first_slice``
+    entries per lane, default ``_ME_TORUS_SLICE``), the later passes are
+    unchanged, and ``multi_exp_grouped_finish`` maps the per-window rows back
+    by ``gt_pi``: the same results, bit for bit."""
     dev = a.device
+    torus = a.shape[-1] == 48
+    sl = first_slice or (_ME_TORUS_SLICE if torus else _ME_SLICE)
     G = len(groups)
     if c is None:
         W, c = me_window(tuple(groups))
-    B, lay, overflow = _device_buckets(k, group, groups, W, c, _ME_SLICE, lambda items: _gt_ops(a, items, item_split))
+    B, lay, overflow = _device_buckets(k, group, groups, W, c, sl, lambda items: _gt_ops(a, items, item_split))
     if "gtw" not in lay:
         lay["gtw"] = _chunk_weight_plan(lay["used"], c, dev)
     wp = lay["gtw"]
@@ -523,7 +552,7 @@ def multi_exp_device(a: torch.Tensor, k: torch.Tensor, group, groups: tuple, W: 
         cur = gt_slice_prod(cur, None, st, ln)                            # chunks -> (group, window)
     win = gt_one(dev).repeat(G * W, 1)
     win.index_copy_(0, wp["gws"], cur)
-    return {"G": G, "W": W, "c": c, "win": win.view(1, G * W, 96), "overflow": overflow}
+    return {"G": G, "W": W, "c": c, "win": win.view(1, G * W, 96), "overflow": overflow, "torus": torus}
 
 
 def multi_exp_grouped_finish(h) -> torch.Tensor:
@@ -531,7 +560,10 @@ def multi_exp_grouped_finish(h) -> torch.Tensor:
     G, W = h["G"], h["W"]
     if h["win"] is None:
         return gt_one("cpu").repeat(G, 1)
-    S_w = gt_prod(h["win"].cpu(), chunk=64).view(G, W, 96)  # host: one chain per (group, window)
+    S_w = gt_prod(h["win"].cpu(), chunk=64)                 # host: one chain per (group, window)
+    if h.get("torus"):                                      # numerators -> the canonical unitary values
+        S_w = gt_pi(S_w)
+    S_w = S_w.view(G, W, 96)
     acc = S_w[:, W - 1].contiguous()
     sh = _pow2_scalar(h["c"]).expand(G, 8).contiguous()
     for w in range(W - 2, -1, -1):

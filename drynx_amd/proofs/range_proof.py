@@ -1181,6 +1181,8 @@ def verify_range_proof_list_multi(r: RangeProofList, sigmat: SigMaterial, P_poin
             with timers.span("rp.verify.useg_items"):
                 useg = _useg_items(msq)
         with timers.span("rp.verify.segments"):
+            if A2 is None:  # torus first pass: the segment passes' Fp12 rows only now
+                A2 = _stack_frob8(r.A)
             x = dict(A2=A2, rho=rho_all, ab=ab_all, gam=gam_all, w=w_all, Cp=Cp, z=z, useg=useg, u_seg=msq["u_seg"],
                      # the segment pass keeps host-planned 11-bit windows (its groups are
                      # (VN, segment) pairs: 16-bit windows would mean millions of buckets)
@@ -1288,16 +1290,40 @@ def _pass_r(V, zphi, rho, meta):
         return nt.g2_msm_device(V, s_r, m, ((m, 254),) * G, c=cR)
 
 
+_ME_TORUS_DEFAULT = "1"  # measured: profiles/me_torus/README.md
+
+
+def _me_torus() -> bool:
+    """DRYNX_ME_TORUS=1: the first pass of the GT multi-exponentiation runs on
+    torus images of the a_ij (csrc/kernels/dx_me_torus.hip); 0: on the Fp12
+    rows.  Same results bit for bit: the a_ij that ``validate_list`` accepts
+    are unitary, a row it rejects either fails the batch before GG is used
+    (no ``segs``) or carries zero weights (``segs``) and enters no bucket."""
+    return os.environ.get("DRYNX_ME_TORUS", _ME_TORUS_DEFAULT) == "1"
+
+
+def _stack_frob8(A: torch.Tensor) -> torch.Tensor:
+    """(A, frob^8 A) stacked [2m, 96]: the Frobenius image written in place."""
+    m = A.shape[0]
+    A2 = torch.empty((2 * m, 96), dtype=torch.int32, device=A.device)
+    A2[:m].copy_(A)
+    nt.gt_frob8(A.contiguous(), out=A2[m:])
+    return A2
+
+
 def _pass_me(A, ab, gam, rho, zv, w, zr, z, meta):
     """The GT multi-exponentiation over (A, frob^8 A) with the GLV halves of
     rho (groups 0..G-1) and each VN's 40-bit membership combination (G..2G-1),
-    and the Fr exponent sums, on the current stream -> (A2, mexp, e_all, dfull)."""
+    and the Fr exponent sums, on the current stream -> (A2, mexp, e_all, dfull).
+    On the torus path (``_me_torus``) the source is the stacked torus images
+    instead and A2 is None: only a failing batch's segment passes need it
+    (``_stack_frob8``)."""
     G, m, S, l, gb, wc, cR = meta
     dev = A.device
-    with timers.span("rp.frob8"):  # (A, frob^8 A) stacked: the Frobenius image written in place
-        A2 = torch.empty((2 * m, 96), dtype=torch.int32, device=dev)
-        A2[:m].copy_(A)
-        nt.gt_frob8(A.contiguous(), out=A2[m:])
+    torus = _me_torus()
+    with timers.span("rp.frob8"):
+        A2 = None if torus else _stack_frob8(A)
+        src = nt.gt_beta_rows(A) if torus else A2
     abv = ab.view(G, m, 2)
     k = torch.zeros((3 * G * m, 8), dtype=torch.int32, device=dev)
     kr = k[: 2 * G * m].view(G, 2 * m, 8)
@@ -1308,7 +1334,7 @@ def _pass_me(A, ab, gam, rho, zv, w, zr, z, meta):
                         lambda e: torch.where(e < 2 * G * m, e // (2 * m), G + (e - 2 * G * m) // m).to(torch.int32),
                         3 * G * m)
     with timers.span("rp.run.ME"):
-        mexp = nt.multi_exp_device(A2, k, mgrp, ((2 * m, 32),) * G + ((m, gb),) * G, wc[0], wc[1],
+        mexp = nt.multi_exp_device(src, k, mgrp,((2 * m, 32),) * G + ((m, gb),) * G, wc[0], wc[1],
                                    item_split=(2 * G * m, m))
     e_all = nt.fr_dot_rows(rho, zv, G, b_periodic=True)                                 # sum rho Zv per VN
     dfull = torch.stack([nt.fr_dot_rows(w, zr, G, b_periodic=True),
