@@ -139,6 +139,7 @@ _SIGS = {
     "dx_fold_steps": [],
     "dx_rp_coeffs": [_P, _P, _P, _L],
     "dx_int_moments": [_I, _P, _P, _L, _I, _P, _L, _P, _I, _P, _P],
+    "dx_extreme_digit_bits": [_I, _P, _P, _L, _P, _L, _P, _L, _I, _L, _L, _L, _L, _L, _L, _P, _P],
     "dx_sha256_rows": [_I, _P, _P, _L, _L, _L, _L, _P],
     "dx_sha256_segments": [_I, _P, _P, _L, _L, _L, _P],
     "dx_g1_aff_to_uv": [_I, _P, _P, _L],
@@ -190,14 +191,15 @@ def loaded_path() -> str:
 _keep = threading.local()
 
 
-def _ptr(t: torch.Tensor | None):
+def _ptr(t: torch.Tensor | None, strided: bool = False):
     """Raw pointer of a contiguous tensor for a native call.  The tensor is
     kept alive until the calling thread's next ``_call`` returns: a temporary
     such as ``_ptr(x.contiguous())`` would otherwise be freed before the call
-    runs (on the host path the native code would then read freed memory)."""
+    runs (on the host path the native code would then read freed memory).
+    ``strided``: the op takes the tensor's strides itself."""
     if t is None:
         return None
-    assert t.is_contiguous(), "native ops need contiguous tensors"
+    assert strided or t.is_contiguous(), "native ops need contiguous tensors"
     held = getattr(_keep, "held", None)
     if held is None:
         held = _keep.held = []
@@ -1143,6 +1145,27 @@ def _upload(a: np.ndarray, device) -> torch.Tensor:
     return t
 
 
+def _tile_plan(counts: np.ndarray):
+    """Host-made tile plan of the segmented reductions: ``([n_tiles, 3] int64
+    rows (segment, row0, row1), [G + 1] first tile of every segment)``.  Tiles
+    are row ranges of one segment, sized so a big DP spreads over ~2k
+    workgroups and each tile still streams >= 64 rows; a segment's tiles are
+    consecutive and an empty segment has none."""
+    G = len(counts)
+    if G == 0:
+        return np.zeros((0, 3), dtype=np.int64), np.zeros(1, dtype=np.int64)
+    per_tile = -(-int(counts.sum()) // 2048)
+    chunk = max(64, (per_tile + 63) // 64 * 64)
+    per = np.maximum(1, -(-counts // chunk)) * (counts > 0)
+    seg = np.repeat(np.arange(G, dtype=np.int64), per)
+    starts = np.concatenate([[0], np.cumsum(counts)[:-1]]).astype(np.int64)
+    first = np.concatenate([[0], np.cumsum(per)]).astype(np.int64)
+    k = np.arange(len(seg), dtype=np.int64) - np.repeat(first[:-1], per)
+    r0 = np.repeat(starts, per) + k * chunk
+    r1 = np.minimum(r0 + chunk, np.repeat(starts + counts, per))
+    return np.stack([seg, r0, r1], axis=1).reshape(-1, 3).astype(np.int64), first
+
+
 def int_moments(Z: torch.Tensor, seg_rows, pairs) -> torch.Tensor:
     """K14 (csrc/kernels/dx_moments.hip): exact int64 ``out[g, p] = sum over the
     rows of segment g of Z[i, a_p] * Z[i, b_p]`` (mod 2^64), column index
@@ -1159,27 +1182,67 @@ def int_moments(Z: torch.Tensor, seg_rows, pairs) -> torch.Tensor:
     if counts.sum() != Z.shape[0]:
         raise ValueError(f"int_moments: segments cover {counts.sum()} rows, Z has {Z.shape[0]}")
     out = torch.zeros((G, P), dtype=torch.int64, device=Z.device)
-    # tiles: row ranges of one segment, sized so a big DP spreads over ~2k
-    # workgroups and each tile still streams >= 64 rows
-    per_tile = -(-int(counts.sum()) // 2048)
-    chunk = max(64, (per_tile + 63) // 64 * 64)
-    per = np.maximum(1, -(-counts // chunk)) * (counts > 0)
-    seg = np.repeat(np.arange(G, dtype=np.int64), per)
-    starts = np.concatenate([[0], np.cumsum(counts)[:-1]]).astype(np.int64)
-    first = np.concatenate([[0], np.cumsum(per)[:-1]]).astype(np.int64)
-    k = np.arange(len(seg), dtype=np.int64) - np.repeat(first, per)
-    r0 = np.repeat(starts, per) + k * chunk
-    r1 = np.minimum(r0 + chunk, np.repeat(starts + counts, per))
-    n_tiles = len(seg)
+    plan, _ = _tile_plan(counts)
+    n_tiles = len(plan)
     if n_tiles == 0:
         return out
     Zc = Z.contiguous()
-    tiles = _upload(np.stack([seg, r0, r1], axis=1), Z.device)
+    tiles = _upload(plan, Z.device)
     pairs_t = _upload(pr, Z.device)
     g, s = _ctx(Zc)
     partial = None if g else torch.empty((n_tiles, P), dtype=torch.int64)
     _call("dx_int_moments", g, s, _ptr(Zc), Zc.stride(0), C, _ptr(tiles), n_tiles, _ptr(pairs_t), P, _ptr(out),
           _ptr(partial))
+    return out
+
+
+EXTREME_MAX_BASE = 65536
+EXTREME_MAX_RANGE = 1 << 40
+
+
+def extreme_digit_bits(Z: torch.Tensor, seg_rows, is_max: bool, qmin: int, qmax: int, base: int, round: int,
+                       prefix: int) -> torch.Tensor:
+    """K14b (csrc/kernels/dx_extreme.hip): the [G, base] int64 rows every DP of a
+    batch encrypts in round ``round`` of the iterative min/max query.
+
+    Z [rows, n_in] holds the DPs' records back to back (``seg_rows[g]`` rows for
+    DP g; only column 0 is read, through Z's row stride).  With R = qmax - qmin
+    + 1 and L the smallest integer with base^L >= R, DP g's clamped extreme e
+    gives o = e - qmin; if o div base^(L-round) == prefix its value v is the
+    digit (o div base^(L-1-round)) mod base, otherwise (and for a DP without
+    records) v is neutral: 0 for max, base for min.  Row g is the unary encoding
+    of v over [0, base-1]: [i < v] for max, [i >= v] for min.  Two launches for
+    all DPs (tile partials, then the rows); the tile plan is int_moments'."""
+    assert Z.dtype == torch.int64 and Z.dim() == 2
+    qmin, qmax, base, k, prefix = int(qmin), int(qmax), int(base), int(round), int(prefix)
+    R = qmax - qmin + 1
+    if not 2 <= base <= EXTREME_MAX_BASE or not 1 <= R <= EXTREME_MAX_RANGE:
+        raise ValueError(f"extreme_digit_bits: base {base}, {R} values")
+    L, p = 1, base
+    while p < R:
+        p *= base
+        L += 1
+    if not 0 <= k < L or not 0 <= prefix < base ** k:
+        raise ValueError(f"extreme_digit_bits: round {k} of {L}, prefix {prefix}")
+    counts = np.asarray(seg_rows, dtype=np.int64).reshape(-1)
+    G = len(counts)
+    if counts.sum() != Z.shape[0] or (G and counts.min() < 0):
+        raise ValueError(f"extreme_digit_bits: segments cover {counts.sum()} rows, Z has {Z.shape[0]}")
+    if Z.shape[0] and Z.shape[1] < 1:
+        raise ValueError("extreme_digit_bits: Z has no column")
+    out = torch.empty((G, base), dtype=torch.int64, device=Z.device)
+    if G == 0:
+        return out
+    plan, first = _tile_plan(counts)
+    n_tiles = len(plan)
+    # one upload: the tiles, then every DP's tile range
+    desc = _upload(np.concatenate([plan.reshape(-1), first]), Z.device)
+    partial = torch.empty((max(1, n_tiles),), dtype=torch.int64, device=Z.device)
+    g, s = _ctx(out)
+    # (Z is read in place: a view's row stride is the kernel's ldz)
+    _call("dx_extreme_digit_bits", g, s, _ptr(Z, strided=True), Z.stride(0) if Z.shape[0] > 1 else 1,
+          _ptr(desc[: 3 * n_tiles]), n_tiles, _ptr(desc[3 * n_tiles:]), G, 1 if is_max else 0, qmin, qmax, base,
+          base ** (L - k), base ** (L - 1 - k), prefix, _ptr(partial), _ptr(out))
     return out
 
 

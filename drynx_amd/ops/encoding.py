@@ -220,6 +220,35 @@ def batch_values(name: str, Z: torch.Tensor, seg_rows, qmin: int = 0, qmax: int 
     raise ValueError(f"{name} has no batched encoder")
 
 
+def extreme_digit_values(operation: Operation, Z: torch.Tensor, seg_rows, base: int, rnd: int,
+                         prefix: int) -> torch.Tensor:
+    """[n_dp, base] int64 values of one round of the iterative min/max
+    (``SurveyQuery.IterBase``): per DP the 0/1 values the unary encoders above
+    emit for its round value over the domain [0, base-1] -- the base-``base``
+    digit ``rnd`` of its clamped extreme if the leading digits equal
+    ``prefix``, the neutral value otherwise.  Two launches for every DP of the
+    batch and no torch op in between (``native.extreme_digit_bits``); the host
+    path runs the same entry."""
+    from .. import native as nt
+
+    if operation.NameOp not in ("min", "max"):
+        raise ValueError(f"{operation.NameOp} has no iterative rounds")
+    return nt.extreme_digit_bits(Z, seg_rows, operation.NameOp == "max", operation.QueryMin, operation.QueryMax,
+                                 base, rnd, prefix)
+
+
+def encode_extreme_digit(data, operation: Operation, base: int, rnd: int, prefix: int, pk, with_proofs=False,
+                         ranges=None):
+    """One DP's response to a round of the iterative min/max: the values of
+    ``extreme_digit_values`` for its records, OR-encoded (min) or AND-encoded
+    (max) as ``encode_min`` / ``encode_max`` encode theirs."""
+    x = _t(data[0], pk.device).reshape(-1).to(torch.int64)
+    vals = extreme_digit_values(operation, x[:, None], [x.numel()], base, rnd, prefix)[0].cpu().tolist()
+    if operation.NameOp == "min":
+        return encode_bits([v != 0 for v in vals], pk, "or", with_proofs, ranges)
+    return encode_bits([v == 0 for v in vals], pk, "and", with_proofs, ranges)  # values are the inverted AND bits
+
+
 def encrypt_batch(pk: eg.PublicKeyTable, values: torch.Tensor, bits: bool):
     """One encryption launch for a whole batch: ints (EncryptIntVectorGetRs),
     or for bit encodings without proofs a fresh random non-zero scalar where the

@@ -48,6 +48,13 @@ def _seed(survey_id: str, dp_id: str) -> int:
     return zlib.crc32(f"{survey_id}/{dp_id}".encode()) & 0x7FFFFFFF
 
 
+def data_seed_id(sq) -> str:
+    """The id a DP's generated records are seeded from: the survey's, or for a
+    round of an iterative min/max the id its rounds share (every round has a
+    survey id of its own and must still see the same records)."""
+    return sq.IterSurveyID if sq.IterBase else sq.SurveyID
+
+
 def generate_fake_data(op, nbr_rows: int, lo: int, hi: int, device, gen: torch.Generator):
     """createFakeDataForOperation: NbrInput columns of uniform ints in [lo, hi]."""
     n_in = max(1, op.NbrInput)
@@ -82,7 +89,7 @@ def dp_encode(ctx, sq, dp, sync_timer: bool = True) -> dict:
     op = q.Operation
     device = ctx.device
     pk = eg.pk_table(sq.RosterServers.aggregate(), device)
-    gen = torch.Generator().manual_seed(_seed(sq.SurveyID, dp.id))
+    gen = torch.Generator().manual_seed(_seed(data_seed_id(sq), dp.id))
     data = lr = None
     if op.NameOp == "logistic regression":
         if ctx.dp_data and dp.id in ctx.dp_data:
@@ -108,7 +115,11 @@ def dp_encode(ctx, sq, dp, sync_timer: bool = True) -> dict:
     cvs, proofs, clears = [], [], []
     with timers.timed(f"{dp.id}_DPencoding", sync=sync_timer):
         for _ in groups:
-            r = enc.encode(data, pk, op_eff, ranges=q.Ranges, with_proofs=with_proofs, lr_data=lr)
+            if sq.IterBase:
+                r = enc.encode_extreme_digit(data, op, sq.IterBase, sq.IterRound, sq.IterPrefix, pk, with_proofs,
+                                             q.Ranges)
+            else:
+                r = enc.encode(data, pk, op_eff, ranges=q.Ranges, with_proofs=with_proofs, lr_data=lr)
             cv = r.cv
             if cf:
                 cv = eg.CipherVector.cat([cv] * cf)
@@ -150,7 +161,7 @@ def dp_encode_batch(ctx, sq, dps: list) -> dict:
             cols = [enc._t(c, device).reshape(-1).to(torch.int64) for c in ctx.dp_data[dp.id]]
             mats.append(torch.stack(cols, dim=1))
         else:  # generate_fake_data's draw, kept on the host until the one upload below
-            gen = torch.Generator().manual_seed(_seed(sq.SurveyID, dp.id))
+            gen = torch.Generator().manual_seed(_seed(data_seed_id(sq), dp.id))
             t = torch.randint(g.GenerateDataMin, g.GenerateDataMax + 1, (n_in, max(1, g.GenerateRows)), generator=gen,
                               dtype=torch.int64)
             mats.append(t.t())
@@ -161,7 +172,10 @@ def dp_encode_batch(ctx, sq, dps: list) -> dict:
             Z = Z.pin_memory().to(device, non_blocking=True)
     else:
         Z = torch.cat([m.to(device) for m in mats]).contiguous()
-    vals = enc.batch_values(op.NameOp, Z, rows, op.QueryMin, op.QueryMax)  # [n_dp, n_out]
+    if sq.IterBase:  # one round of the iterative min/max: [n_dp, IterBase] from the K14b kernel pair
+        vals = enc.extreme_digit_values(op, Z, rows, sq.IterBase, sq.IterRound, sq.IterPrefix)
+    else:
+        vals = enc.batch_values(op.NameOp, Z, rows, op.QueryMin, op.QueryMax)  # [n_dp, n_out]
     return _encode_batch_tail(ctx, sq, dps, vals, groups, pk)
 
 

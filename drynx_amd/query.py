@@ -189,6 +189,17 @@ class SurveyQuery:
     # checks every V_ij in G2; 2 = strict with the v2 transcript, whose
     # challenge also binds D and every V_ij, a_ij (range_proof.go:350-374 omits them).
     RangeProofMode: int = 0
+    # extension: iterative min/max.  IterBase b > 0 makes the query ONE round of
+    # a digit-by-digit search: the DPs answer with the unary encoding (b
+    # outputs) of the IterRound-th base-b digit of their extreme, most
+    # significant first, if its leading digits equal IterPrefix, and with the
+    # neutral value otherwise (csrc/kernels/dx_extreme.hip).  IterSurveyID is
+    # the id the rounds of one search share: generated records are seeded from
+    # it, so every round sees the same data.  0 = the reference's one-shot query.
+    IterBase: int = 0
+    IterRound: int = 0
+    IterPrefix: int = 0
+    IterSurveyID: str = ""
 
     # -------------------------------------------------------------- helpers
     def all_dps(self):
@@ -289,6 +300,10 @@ def _survey_from_dict(d: dict) -> SurveyQuery:
         KeySwitchingProofThreshold=d.get("KeySwitchingProofThreshold", 0.0),
         VerificationSharding=d.get("VerificationSharding", 0),
         RangeProofMode=d.get("RangeProofMode", 0),
+        IterBase=d.get("IterBase", 0),
+        IterRound=d.get("IterRound", 0),
+        IterPrefix=d.get("IterPrefix", 0),
+        IterSurveyID=d.get("IterSurveyID", ""),
     )
 
 
@@ -365,11 +380,64 @@ def check_parameters(sq: SurveyQuery, diffp: bool) -> bool:
             D = lrp.NbrFeatures + 1
             if len(lrp.InitialWeights or []) not in (0, D, max(1, nt) * D):
                 msg.append("initial weights are neither empty, one vector of d + 1 nor one per target")
+    msg += _check_iterative(sq)
     if q.Operation.QueryMin != q.DPDataGen.GenerateDataMin or q.Operation.QueryMax != q.DPDataGen.GenerateDataMax:
         msg.append("min or max are inconsistent at DP and operations")
     for m in msg:
         log.warning(m)
     return not msg
+
+
+ITER_MAX_BASE = 65536
+ITER_MAX_RANGE = 1 << 40  # every power of the base a round divides by stays far inside int64
+
+
+def iter_rounds(qmin: int, qmax: int, base: int) -> int:
+    """Rounds L of the iterative min/max over [qmin, qmax] in base ``base``: the
+    smallest integer with base^L >= qmax - qmin + 1 (integer products, no log)."""
+    R = int(qmax) - int(qmin) + 1
+    base = int(base)
+    if base < 2 or R < 1:
+        raise ValueError(f"no iterative rounds for base {base} over {R} values")
+    L, p = 1, base
+    while p < R:
+        p *= base
+        L += 1
+    return L
+
+
+def _check_iterative(sq: SurveyQuery) -> list:
+    """Rules of the iterative min/max extension (IterBase > 0); nothing when it is off."""
+    b = sq.IterBase
+    if b == 0:
+        if sq.IterRound or sq.IterPrefix:
+            return ["iterative round or prefix without a base"]
+        return []
+    q = sq.Query
+    op = q.Operation
+    msg = []
+    if not isinstance(b, int) or isinstance(b, bool) or not 2 <= b <= ITER_MAX_BASE:
+        return [f"iterative base outside 2..{ITER_MAX_BASE}"]
+    if op.NameOp not in ("min", "max"):
+        msg.append("iterative rounds are defined for min and max only")
+    if q.CuttingFactor != 0:
+        msg.append("iterative rounds with a cutting factor")
+    if add_diff_p(q.DiffP):
+        msg.append("iterative rounds with differential privacy")
+    R = op.QueryMax - op.QueryMin + 1
+    if not 1 <= R <= ITER_MAX_RANGE:
+        msg.append(f"iterative rounds over {R} values (1..2^40)")
+    else:
+        L = iter_rounds(op.QueryMin, op.QueryMax, b)
+        if not isinstance(sq.IterRound, int) or not 0 <= sq.IterRound < L:
+            msg.append(f"iterative round outside 0..{L - 1}")
+        elif not isinstance(sq.IterPrefix, int) or not 0 <= sq.IterPrefix < b ** sq.IterRound:
+            msg.append("iterative prefix is not a number of IterRound digits")
+    if op.NbrOutput != b:
+        msg.append("an iterative round has exactly IterBase outputs")
+    if q.Proofs and (q.Ranges is None or not _ranges_bits(q.Ranges)):
+        msg.append("iterative rounds with proofs need (2, 1) ranges")
+    return msg
 
 
 def query_to_proofs_nbrs(sq: SurveyQuery) -> list:
@@ -413,6 +481,15 @@ def choose_operation(name: str, query_min: int, query_max: int, d: int, cutting_
     if cutting_factor != 0:
         op.NbrOutput = op.NbrOutput * cutting_factor
     return op
+
+
+def iter_operation(name: str, query_min: int, query_max: int, base: int) -> Operation:
+    """The operation of one round of the iterative min/max (extension): the
+    full domain stays in QueryMin/QueryMax, the DPs send ``base`` unary outputs."""
+    if name not in ("min", "max"):
+        raise ValueError(f"Operation: <{name}> has no iterative rounds")
+    iter_rounds(query_min, query_max, base)
+    return Operation(NameOp=name, NbrInput=1, NbrOutput=int(base), QueryMin=int(query_min), QueryMax=int(query_max))
 
 
 MAX_LR_TARGETS = 64

@@ -12,10 +12,12 @@ see services/server.py).
 """
 from __future__ import annotations
 
+import copy
+
 from ..crypto import elgamal as eg
 from ..ops import encoding as enc
 from ..query import (LogisticRegressionParameters, Operation, Query, QueryDiffP, QueryDPDataGen, QueryIVSigs, Roster,
-                     SurveyQuery, new_survey_id)
+                     SurveyQuery, check_parameters, iter_operation, iter_rounds, new_survey_id)
 from ..utils import timers
 
 
@@ -93,6 +95,106 @@ class DrynxClient:
             return decode_logistic_regression_values(vals, op.LRParameters)
         return enc.decode(cv, self.keypair.secret, op, self.table)
 
+    # ------------------------------------------------------------------ iterative min / max
+    def iterative_round_query(self, sq: SurveyQuery, base: int, k: int, prefix: int, iter_id: str) -> SurveyQuery:
+        """Round ``k`` of the iterative min/max search ``iter_id`` as a survey of
+        its own: a copy of ``sq`` (a ``min``/``max`` survey over the full domain)
+        with ``base`` outputs, the first ``base`` columns of its ranges and
+        input-validation signatures (the same objects every round, so the
+        provers' and verifiers' tables built for round 0 serve the others) and
+        a survey id derived from ``iter_id``."""
+        op = sq.Query.Operation
+        rq = copy.copy(sq)
+        rq.Query = copy.copy(sq.Query)
+        rq.Query.Operation = iter_operation(op.NameOp, op.QueryMin, op.QueryMax, base)
+        q = rq.Query
+        if q.Ranges is not None:
+            if len(q.Ranges) < base:
+                raise ValueError(f"{len(q.Ranges)} ranges for {base} outputs per round")
+            q.Ranges = self._iter_columns(sq.Query.Ranges, base)
+        sigs = q.IVSigs.InputValidationSigs
+        if sigs is not None:
+            if any(len(row) < base for row in sigs):
+                raise ValueError(f"input-validation signatures for fewer than {base} outputs per round")
+            cut = self._iter_columns(sigs, base, per_cn=True)
+            q.IVSigs = QueryIVSigs(InputValidationSigs=cut, InputValidationSize1=len(cut), InputValidationSize2=base)
+        rq.IterBase, rq.IterRound, rq.IterPrefix, rq.IterSurveyID = int(base), int(k), int(prefix), iter_id
+        rq.SurveyID = f"{iter_id}.r{k}"  # no '/': ledger buckets and proof keys are '<survey id>/<kind>/...'
+        return rq
+
+    def _iter_columns(self, cols, base: int, per_cn: bool = False):
+        """The first ``base`` columns of a survey's ranges or signature rows, cut
+        once per search (memoised on the source object: the digest cache of
+        the signature broadcast keys on the list's identity)."""
+        if (all(len(row) == base for row in cols) if per_cn else len(cols) == base):
+            return cols
+        memo = getattr(self, "_iter_memo", None)
+        if memo is None:
+            memo = self._iter_memo = {}
+        hit = memo.get((id(cols), base))
+        if hit is not None and hit[0] is cols:
+            return hit[1]
+        cut = [row[:base] for row in cols] if per_cn else [list(r) for r in cols[:base]]
+        if len(memo) > 8:
+            memo.clear()
+        memo[(id(cols), base)] = (cols, cut)
+        return cut
+
+    def send_iterative_extreme(self, sq: SurveyQuery, base: int, on_round=None):
+        """Iterative min/max (extension): the result of the ``min``/``max`` survey
+        ``sq`` found one base-``base`` digit per round, most significant first,
+        instead of one output per value of the domain.  Every round is an
+        ordinary verifiable query with ``base`` unary outputs (its own survey
+        id, proofs and block); round k's query carries the k digits found so
+        far in clear.  Returns ``(value, rounds)``: the decoded extreme and
+        every round's SurveyResult.  ``on_round(k, digit, result)`` is called
+        after each round.  Raises when the DPs' answers contradict an earlier
+        round (a ``min`` round nobody matches) or the groups disagree."""
+        op = sq.Query.Operation
+        L = iter_rounds(op.QueryMin, op.QueryMax, base)
+        is_max = op.NameOp == "max"
+        iter_id = sq.SurveyID or new_survey_id()
+        collective = getattr(getattr(self.entry, "comm", None), "world", 1) > 1
+
+        def digits(partial):
+            """Per group the first zero (max) / non-zero (min) aggregate of the round, None without one."""
+            out = []
+            with timers.timed("Decode"):
+                for cv in partial.groups():
+                    nz = eg.decrypt_check_zero(self.keypair.secret, cv.to(self.device)).cpu().tolist()
+                    out.append(next((i for i, b in enumerate(nz) if (b == 0) == is_max), None))
+            return out
+
+        # With several ranks the others serve exactly L rounds (``serve_iterative_extreme``):
+        # a search that has failed, or found that no DP has records, still runs them all.
+        prefix, rounds, failed, empty = 0, [], None, False
+        for k in range(L):
+            rq = self.iterative_round_query(sq, base, k, prefix, iter_id)
+            if k == 0 and not check_parameters(rq, False):
+                raise ValueError("the iterative query fails CheckParameters")
+            res = self.entry.run_survey(rq, on_result=digits)
+            rounds.append(res)
+            ds = res.client_out
+            digit = ds[0]
+            if failed is None and not empty:
+                if any(d != digit for d in ds):
+                    failed = f"round {k}: the groups disagree on the digit ({ds})"
+                elif digit is None and is_max:
+                    failed = f"round {k}: no zero aggregate (the last output of a max round is always zero)"
+                elif digit is None and k > 0:
+                    failed = f"round {k}: no DP matches the prefix {prefix}: an answer changed between rounds"
+                elif digit is None:
+                    empty = True  # min, round 0: no DP has records -> QueryMin, as the one-shot decode returns
+            if (failed is not None or empty) and not collective:
+                break
+            digit = digit or 0
+            if on_round is not None:
+                on_round(k, digit, res)
+            prefix = prefix * base + digit
+        if failed is not None:
+            raise RuntimeError(f"iterative {op.NameOp} {iter_id}: {failed}")
+        return float(op.QueryMin + (0 if empty else prefix)), rounds
+
     # ------------------------------------------------------------------ VN / skipchain calls
     def send_survey_query_to_vns(self, sq: SurveyQuery):
         """SendSurveyQueryToVNs (api_skipchain.go:16): announce the survey to the
@@ -122,6 +224,19 @@ class DrynxClient:
 
     def send_close_db(self, vn_id: str, remove: bool = False):
         return self.entry.close_db(vn_id, remove)
+
+
+def serve_iterative_extreme(node) -> list:
+    """A rank without the querier serves one iterative min/max search: one
+    ``run_survey(None)`` per round, the number of rounds derived from the
+    first round's query.  Returns the rounds' SurveyResults."""
+    res = node.run_survey(None)
+    sq = node.surveys[res.survey_id]
+    if not sq.IterBase:
+        raise RuntimeError(f"survey {res.survey_id} is not a round of an iterative query")
+    op = sq.Query.Operation
+    L = iter_rounds(op.QueryMin, op.QueryMax, sq.IterBase)
+    return [res] + [node.run_survey(None) for _ in range(L - 1)]
 
 
 def lr_parameters(**kw) -> LogisticRegressionParameters:

@@ -78,6 +78,26 @@ def make_survey(client: DrynxClient, cluster, op_name: str, *, query_min=0, quer
         verification_sharding, range_proof_mode)
 
 
+def make_iterative_survey(client: DrynxClient, cluster, op_name: str, base: int, *, query_min=0, query_max=10,
+                          rows=10, group_by=(1,), proofs=0, thresholds=None, survey_id=None, sig_device="cpu",
+                          deterministic_sigs=False, verification_sharding=0, with_vns=None, range_proof_mode=0):
+    """The survey ``DrynxClient.send_iterative_extreme(sq, base)`` runs in rounds:
+    a ``min``/``max`` over the full domain [query_min, query_max] whose ranges
+    and input-validation signatures cover the ``base`` outputs of a round
+    ((2, 1) each, made once and shared by every round) instead of one per
+    value of the domain."""
+    from ..query import iter_operation
+
+    sq = make_survey(client, cluster, op_name, query_min=query_min, query_max=query_min + base - 1, rows=rows,
+                     group_by=group_by, proofs=proofs, ranges=[2, 1] if proofs else None, thresholds=thresholds,
+                     survey_id=survey_id, sig_device=sig_device, deterministic_sigs=deterministic_sigs,
+                     verification_sharding=verification_sharding, with_vns=with_vns, range_proof_mode=range_proof_mode)
+    sq.Query.Operation = iter_operation(op_name, query_min, query_max, base)
+    sq.Query.DPDataGen.GenerateDataMax = int(query_max)
+    sq.IterBase = int(base)
+    return sq
+
+
 def clear_expected(op_name, clear_dp: dict):
     """Sum of the DPs' clear responses (first group) for checking decoded results."""
     tot = None
@@ -87,4 +107,5 @@ def clear_expected(op_name, clear_dp: dict):
     return tot
 
 
-__all__ = ["local_cluster", "make_survey", "make_signatures", "RANGE_PRESETS", "clear_expected", "O"]
+__all__ = ["local_cluster", "make_survey", "make_iterative_survey", "make_signatures", "RANGE_PRESETS",
+           "clear_expected", "O"]

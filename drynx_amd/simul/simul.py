@@ -22,8 +22,8 @@ import tempfile
 from ..parallel.comm import init_distributed, make_comm
 from ..parallel.netem import flow_hops
 from ..query import QueryDiffP, LogisticRegressionParameters
-from ..services.api import DrynxClient
-from ..services.local import local_cluster, make_survey
+from ..services.api import DrynxClient, serve_iterative_extreme
+from ..services.local import local_cluster, make_iterative_survey, make_survey
 from ..utils import timers
 from ..utils.log import get_logger
 
@@ -116,9 +116,12 @@ def run_row(glob: dict, row: dict, comm, device, workdir, netem: str = "sleep"):
                            Scale=float(row.get("DiffPScale", 1)), Limit=float(row.get("DiffPLimit", 1)))
     results = []
     client = DrynxClient(node, device=device) if comm.rank == 0 else None
+    iter_base = int(row.get("IterBase", 0))  # optional column (extension): iterative min/max in this base
     for rnd in range(int(glob.get("Rounds", 1))):
         t = timers.start_timer("Simulation")
-        if comm.rank == 0:
+        if iter_base:
+            results.append(_run_iterative(row, glob, iter_base, cl, node, client, comm, device, per, proofs))
+        elif comm.rank == 0:
             from ..query import choose_operation
 
             n_out = lr and 0 or choose_operation(op_name, int(row.get("MinData", 0)), int(row.get("MaxData", 1)), d,
@@ -159,6 +162,26 @@ def run_row(glob: dict, row: dict, comm, device, workdir, netem: str = "sleep"):
         timers.end_timer(t)
     node.close(remove=True)
     return results
+
+
+def _run_iterative(row, glob, base, cl, node, client, comm, device, per, proofs):
+    """One iterative min/max search of a runfile row with an ``IterBase`` column
+    (every round a query of its own); returns [value] on rank 0."""
+    if comm.rank != 0:
+        serve_iterative_extreme(node)
+        return None
+    thr_g, thr_o = float(row.get("ThresholdGeneral", 0)), float(row.get("ThresholdOther", 0))
+    sq = make_iterative_survey(client, cl, str(row["OperationName"]), base, query_min=int(row.get("MinData", 0)),
+                               query_max=int(row.get("MaxData", 1)), rows=int(row.get("DPRows", 1)),
+                               group_by=glob.get("GroupByValues", [1]), proofs=proofs,
+                               thresholds=[thr_g, thr_o, thr_o, 0.0, thr_o] if proofs else None, sig_device=device)
+    ids = [p.identity() for p in cl.dps]
+    n_cn = len(cl.cns)
+    sq.ServerToDP = {c.id: ids[i * per:(i + 1) * per] for i, c in enumerate(cl.cns)}
+    if ids[n_cn * per:]:
+        sq.ServerToDP[cl.cns[0].id] += ids[n_cn * per:]
+    value, _ = client.send_iterative_extreme(sq, base)
+    return [value]
 
 
 def main(argv=None):

@@ -94,6 +94,10 @@ def survey_query_to_msg(sq: SurveyQuery) -> dict:
         "VerificationSharding": sq.VerificationSharding,
         "RangeProofMode": sq.RangeProofMode,
         "LRTargets": lr.NbrTargets,
+        "IterBase": sq.IterBase,
+        "IterRound": sq.IterRound,
+        "IterPrefix": sq.IterPrefix,
+        "IterSurveyID": sq.IterSurveyID,
     }
 
 
@@ -134,6 +138,11 @@ def survey_query_from_msg(d: dict) -> SurveyQuery:
         KeySwitchingProofThreshold=d["KeySwitchingProofThreshold"],
         VerificationSharding=d["VerificationSharding"],
         RangeProofMode=d["RangeProofMode"],
+        # absent (a sender without the extension) reads as the classic one-shot query
+        IterBase=int(d.get("IterBase") or 0),
+        IterRound=int(d.get("IterRound") or 0),
+        IterPrefix=int(d.get("IterPrefix") or 0),
+        IterSurveyID=d.get("IterSurveyID") or "",
     )
 
 

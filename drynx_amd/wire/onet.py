@@ -69,8 +69,13 @@ SURVEY_QUERY = (("SurveyID", "string"), ("RosterServers", ("msg", ROSTER)), ("Cl
                 # drynx_amd extension: label columns of a logistic-regression query
                 # (LRParameters.NbrTargets; here, not in LR_PARAMETERS, whose field numbers are stored in blocks)
                 ("LRTargets", "sint"))
-SURVEY_QUERY_TO_VN = (("SQ", ("msg", SURVEY_QUERY)),)
-SURVEY_QUERY_TO_DP = (("SQ", ("msg", SURVEY_QUERY)), ("Root", ("msg", SERVER_IDENTITY)))
+# drynx_amd extension: one round of an iterative min/max query (SurveyQuery.IterBase ...), appended after
+# LRTargets.  This is the schema on the wire; SURVEY_QUERY above stays the field list up to LRTargets, which
+# is what a peer without this extension sends and reads (zero fields are not encoded, unknown ones skipped).
+SURVEY_QUERY_ITER = SURVEY_QUERY + (("IterBase", "sint"), ("IterRound", "sint"), ("IterPrefix", "sint"),
+                                    ("IterSurveyID", "string"))
+SURVEY_QUERY_TO_VN = (("SQ", ("msg", SURVEY_QUERY_ITER)),)
+SURVEY_QUERY_TO_DP = (("SQ", ("msg", SURVEY_QUERY_ITER)), ("Root", ("msg", SERVER_IDENTITY)))
 # VN requests: the reference sends them to the VN's own server; here one entry
 # node hosts many logical VNs, so the VN id is an appended extension field
 END_VERIFICATION_REQUEST = (("QueryInfoID", "string"), ("VN", "string"), ("Timeout", "double"))
@@ -110,7 +115,7 @@ RANGE_PROOF_LIST_BYTES = (("Data", ("ptrslice", ("msg", RANGE_PROOF_BYTES))),)
 
 MESSAGES = {
     "libdrynxrange.RangeProofListBytes": RANGE_PROOF_LIST_BYTES,
-    "libdrynx.SurveyQuery": SURVEY_QUERY,
+    "libdrynx.SurveyQuery": SURVEY_QUERY_ITER,
     "libdrynx.SurveyQueryToVN": SURVEY_QUERY_TO_VN,
     "libdrynx.SurveyQueryToDP": SURVEY_QUERY_TO_DP,
     "libdrynx.EndVerificationRequest": END_VERIFICATION_REQUEST,
