@@ -1,8 +1,12 @@
-// BN254 prime-field arithmetic (Fp and Fr), 8 x 32-bit limbs, Montgomery form.
+// BN254 prime-field arithmetic (Fp and Fr), stored as 8 x 32-bit limbs in
+// Montgomery form (R = 2^256).
 //
-// CDNA4 mapping: every limb product is one `v_mad_u64_u32` (32x32+64 -> 64);
-// the no-carry CIOS variant is valid because both moduli have top word
-// 0x30644e72 < 2^31-1, so the (m*p + t) accumulator never needs a 9th limb.
+// CDNA4 mapping: additions and subtractions run on the 32-bit words with the
+// carry in VCC; a product unpacks its operands into nine 29-bit limbs, so that
+// a whole column of limb products fits one 64-bit accumulator, and every limb
+// product is one `v_mad_u64_u32` (32x32+64 -> 64) with nothing beside it (see
+// "Montgomery products on nine 29-bit limbs" below).  Both moduli are below
+// 2^254, which is what the bounds of that core rest on.
 // One thread owns one field element (8 VGPRs); kernels are thread-per-item.
 //
 // The same inline functions are compiled for the host (CPU batch path used by
@@ -133,238 +137,112 @@ DX_HD FieldT<PR> fdbl(const FieldT<PR> &a) {
   return fadd(a, a);
 }
 
-#ifdef __HIP_DEVICE_COMPILE__
-// acc(64) + hi(32) += x * y: one v_mad_u64_u32 whose carry-out (SGPR pair)
-// feeds one v_addc_co_u32 -- two instructions per 32x32 partial product
-// (the compiler's lowering of the same C++ needs ~5: a 64-bit add for the
-// carry word plus register-pair moves).
-__device__ __forceinline__ void dx_mac(uint64_t &acc, uint32_t &hi, uint32_t x, uint32_t y) {
-  uint64_t cy, unused;
-  asm("v_mad_u64_u32 %0, %2, %4, %5, %0\n\t"
-      "v_addc_co_u32_e64 %1, %3, %1, 0, %2"
-      : "+v"(acc), "+v"(hi), "=&s"(cy), "=&s"(unused)
-      : "v"(x), "v"(y));
+// ---------------------------------------------------------------------------
+// Montgomery products on nine 29-bit limbs.
+//
+// Storage stays 8 x 32 bits and the Montgomery constant stays R = 2^256.  A
+// product unpacks its operands into nine 29-bit limbs, runs a product-scanning
+// REDC with R' = 2^261 (nine uniform 29-bit digits) on (a << 5) * b, and packs
+// the result back: ((a << 5) b + m p) / 2^261 = (a b + m' p) / 2^256 mod p.
+// A limb product is below 2^58, so a whole column (up to 27 of them plus the
+// carry of the previous column) fits one uint64_t: there is no carry word, no
+// add-with-carry per limb product and no inline asm, and the host runs the
+// same code.  Each `acc += (uint64_t)x * y` is one v_mad_u64_u32 on gfx950.
+namespace l29 {
+constexpr uint32_t M29 = (1u << 29) - 1;
+
+// bits [29 k, 29 k + 29) of a little-endian 8 x 32-bit integer (compile time)
+constexpr uint32_t climb(const uint32_t (&w)[8], int k) {
+  uint32_t r = 0;
+  for (int b = 0; b < 29; b++) {
+    const int bit = 29 * k + b;
+    if (bit < 256 && ((w[bit / 32] >> (bit % 32)) & 1u)) r |= 1u << b;
+  }
+  return r;
 }
 
-// Two to four MACs in ONE asm statement.  The hazard recognizer pads the
-// boundary between two inline-asm statements with an s_nop (it cannot see
-// that the next block only reads VGPRs), which cost one issue slot per MAC
-// when every MAC was its own statement; inside a statement the mad -> addc
-// carry hand-off needs no wait state (validated bit-exact against the oracle).
-#define DX_MAC_STEP(X, Y) "v_mad_u64_u32 %0, %2, %" #X ", %" #Y ", %0\n\tv_addc_co_u32_e64 %1, %3, %1, 0, %2\n\t"
-// YC = "v": both factors in VGPRs; YC = "s": the second factor is a uniform
-// constant (a modulus limb) read from an SGPR, so it occupies no VGPR.
-#define DX_MAC_FNS(SUF, YC)                                                                                      \
-  __device__ __forceinline__ void dx_mac1##SUF(uint64_t &acc, uint32_t &hi, uint32_t x0, uint32_t y0) {          \
-    uint64_t cy, unused;                                                                                         \
-    asm(DX_MAC_STEP(4, 5) : "+v"(acc), "+v"(hi), "=&s"(cy), "=&s"(unused) : "v"(x0), YC(y0));                   \
-  }                                                                                                              \
-  __device__ __forceinline__ void dx_mac2##SUF(uint64_t &acc, uint32_t &hi, uint32_t x0, uint32_t y0, uint32_t x1, \
-                                               uint32_t y1) {                                                    \
-    uint64_t cy, unused;                                                                                         \
-    asm(DX_MAC_STEP(4, 5) DX_MAC_STEP(6, 7)                                                                      \
-        : "+v"(acc), "+v"(hi), "=&s"(cy), "=&s"(unused) : "v"(x0), YC(y0), "v"(x1), YC(y1));                    \
-  }                                                                                                              \
-  __device__ __forceinline__ void dx_mac3##SUF(uint64_t &acc, uint32_t &hi, uint32_t x0, uint32_t y0, uint32_t x1, \
-                                               uint32_t y1, uint32_t x2, uint32_t y2) {                          \
-    uint64_t cy, unused;                                                                                         \
-    asm(DX_MAC_STEP(4, 5) DX_MAC_STEP(6, 7) DX_MAC_STEP(8, 9)                                                    \
-        : "+v"(acc), "+v"(hi), "=&s"(cy), "=&s"(unused)                                                          \
-        : "v"(x0), YC(y0), "v"(x1), YC(y1), "v"(x2), YC(y2));                                                    \
-  }                                                                                                              \
-  __device__ __forceinline__ void dx_mac4##SUF(uint64_t &acc, uint32_t &hi, uint32_t x0, uint32_t y0, uint32_t x1, \
-                                               uint32_t y1, uint32_t x2, uint32_t y2, uint32_t x3, uint32_t y3) { \
-    uint64_t cy, unused;                                                                                         \
-    asm(DX_MAC_STEP(4, 5) DX_MAC_STEP(6, 7) DX_MAC_STEP(8, 9) DX_MAC_STEP(10, 11)                                \
-        : "+v"(acc), "+v"(hi), "=&s"(cy), "=&s"(unused)                                                          \
-        : "v"(x0), YC(y0), "v"(x1), YC(y1), "v"(x2), YC(y2), "v"(x3), YC(y3));                                   \
-  }
-#define DX_YV(y) "v"(y)
-#define DX_YS(y) "s"(y)
-DX_MAC_FNS(_vv, DX_YV)
-DX_MAC_FNS(_vs, DX_YS)
-
-// Column accumulator that batches queued MACs into 4-MAC asm statements, one
-// queue for products of two variables and one for products by a modulus limb.
-// Loops around it are fully unrolled, so the counts are compile-time
-// constants at every call and the switches fold away.
-struct MacQ {
-  uint64_t acc = 0;
-  uint32_t hi = 0;
-  uint32_t xv[4], yv[4], xs[4], ys[4];
-  int nv = 0, ns = 0;
-  __device__ __forceinline__ void push(uint32_t a, uint32_t b) {
-    xv[nv] = a;
-    yv[nv] = b;
-    if (++nv == 4) flush_v();
-  }
-  __device__ __forceinline__ void push_mod(uint32_t a, uint32_t modlimb) {
-    xs[ns] = a;
-    ys[ns] = modlimb;
-    if (++ns == 4) flush_s();
-  }
-  __device__ __forceinline__ void flush_v() {
-    switch (nv) {
-      case 1: dx_mac1_vv(acc, hi, xv[0], yv[0]); break;
-      case 2: dx_mac2_vv(acc, hi, xv[0], yv[0], xv[1], yv[1]); break;
-      case 3: dx_mac3_vv(acc, hi, xv[0], yv[0], xv[1], yv[1], xv[2], yv[2]); break;
-      case 4: dx_mac4_vv(acc, hi, xv[0], yv[0], xv[1], yv[1], xv[2], yv[2], xv[3], yv[3]); break;
-      default: break;
-    }
-    nv = 0;
-  }
-  __device__ __forceinline__ void flush_s() {
-    switch (ns) {
-      case 1: dx_mac1_vs(acc, hi, xs[0], ys[0]); break;
-      case 2: dx_mac2_vs(acc, hi, xs[0], ys[0], xs[1], ys[1]); break;
-      case 3: dx_mac3_vs(acc, hi, xs[0], ys[0], xs[1], ys[1], xs[2], ys[2]); break;
-      case 4: dx_mac4_vs(acc, hi, xs[0], ys[0], xs[1], ys[1], xs[2], ys[2], xs[3], ys[3]); break;
-      default: break;
-    }
-    ns = 0;
-  }
-  __device__ __forceinline__ void flush() {
-    flush_v();
-    flush_s();
-  }
-  // flush, emit the low word of the column, shift the 96-bit accumulator
-  __device__ __forceinline__ uint32_t next_column() {
-    flush();
-    const uint32_t lo = (uint32_t)acc;
-    acc = (acc >> 32) | ((uint64_t)hi << 32);
-    hi = 0;
-    return lo;
-  }
+// Limbs of the modulus and -MOD^-1 mod 2^29 (the low 29 bits of the 32-bit
+// Montgomery constant).  MOD < 2^254, so P[8] < 2^22.
+template <class PR>
+struct Mod {
+  static constexpr uint32_t P[9] = {climb(PR::MOD, 0), climb(PR::MOD, 1), climb(PR::MOD, 2),
+                                    climb(PR::MOD, 3), climb(PR::MOD, 4), climb(PR::MOD, 5),
+                                    climb(PR::MOD, 6), climb(PR::MOD, 7), climb(PR::MOD, 8)};
+  static constexpr uint32_t NINV = PR::INV & M29;
 };
 
-// Montgomery multiplication on gfx950: finely integrated product scanning
-// (column-wise Comba, Montgomery digits m_i folded into the same columns) with
-// one 96-bit column accumulator: ~360 VALU instructions per product instead of
-// ~900 for the compiler-lowered CIOS loop (measured: +20% Miller loops/s,
-// +30% G1 scalar multiplications/s).  A second, interleaved accumulator per
-// column was measured slower: these kernels are issue-bound, not
-// latency-bound.  a, b < MOD -> result < MOD.
-template <class PR>
-__device__ __forceinline__ FieldT<PR> fmul(const FieldT<PR> &a, const FieldT<PR> &b) {
-  uint32_t m[8], u[8];
-  MacQ q;
+// L[k] = bits [29 k, 29 k + 29) of (w << SH), SH in {0, 5}, for any w < 2^256.
+// Out: L[0..8] < 2^29; for SH = 0, L[8] < 2^24.  Every shift count is a
+// compile-time constant in [0, 31]: the low limb of a pre-shifted value is a
+// left shift of word 0 alone, a limb that starts at bit s <= 3 of its word
+// needs no second word, and limb 8 ends in word 7.
+template <int SH>
+DX_HD void unpack(const uint32_t *w, uint32_t *L) {
+  static_assert(SH == 0 || SH == 5, "pre-shift is 0 or 5 bits");
 #pragma unroll
-  for (int i = 0; i < 8; i++) {
-#pragma unroll
-    for (int j = 0; j < i; j++) {
-      q.push(a.v[j], b.v[i - j]);
-      q.push_mod(m[j], PR::MOD[i - j]);
+  for (int k = 0; k < 9; k++) {
+    const int lo = 29 * k - SH;  // first bit of w in limb k
+    if (lo < 0) {
+      L[k] = (w[0] << SH) & M29;
+    } else {
+      const int j = lo / 32, s = lo % 32;
+      uint32_t x = w[j] >> s;
+      if (s > 3 && j + 1 < 8) x |= w[j + 1] << (32 - s);
+      L[k] = x & M29;
     }
-    q.push(a.v[i], b.v[0]);
-    q.flush();
-    m[i] = (uint32_t)q.acc * PR::INV;
-    q.push_mod(m[i], PR::MOD[0]);
-    (void)q.next_column();
   }
+}
+
+// The column loop: REDC_{2^261}(A B [+ C D]) on limbs.
+// In : A, C < 2^29 per limb (a value << 5); B, D < 2^29 per limb, values
+//      below 2^256.
+// Col: at most 9 (A B) + 9 (C D) + 9 (m P) products below 2^58 plus a carry
+//      below 2^36: < 27 * 2^58 + 2^36 < 2^63.
+// Out: u[0..7] < 2^29 and u[8], the value ((a << 5) b [+ (c << 5) d] + m p)
+//      / 2^261 < (a b [+ c d]) / 2^256 + p.  For a, c < 2^256 and b, d < p
+//      that is below 2 p [3 p], so u[8] < 2^24 and pack() is exact; for
+//      a, b, c, d < p it is below 1.2 p [1.4 p].
+template <class PR, bool TWO>
+DX_HD void redc_cols(const uint32_t *A, const uint32_t *B, const uint32_t *C, const uint32_t *D, uint32_t *u) {
+  using MP = Mod<PR>;
+  uint32_t m[9];
+  uint64_t acc = 0;
 #pragma unroll
-  for (int i = 8; i < 16; i++) {
+  for (int i = 0; i < 9; i++) {
 #pragma unroll
-    for (int j = i - 7; j < 8; j++) {
-      q.push(a.v[j], b.v[i - j]);
-      q.push_mod(m[j], PR::MOD[i - j]);
+    for (int j = 0; j <= i; j++) {
+      acc += (uint64_t)A[j] * B[i - j];
+      if (TWO) acc += (uint64_t)C[j] * D[i - j];
+      if (j < i) acc += (uint64_t)m[j] * MP::P[i - j];
     }
-    u[i - 8] = q.next_column();
+    m[i] = ((uint32_t)acc * MP::NINV) & M29;
+    acc += (uint64_t)m[i] * MP::P[0];
+    acc >>= 29;
   }
-  // result = u + 2^256 * acc < 2 MOD: one conditional subtraction
-  uint32_t s[8], br = 0;
 #pragma unroll
-  for (int i = 0; i < 8; i++) s[i] = subb32(u[i], PR::MOD[i], br);
-  const bool keep = ((uint32_t)q.acc == 0) && br;  // u < MOD and no overflow word
-  FieldT<PR> r;
+  for (int i = 9; i < 17; i++) {
 #pragma unroll
-  for (int i = 0; i < 8; i++) r.v[i] = keep ? u[i] : s[i];
-  return r;
-}
-
-// Lazy reduction (device): the 512-bit product and the Montgomery reduction
-// as separate steps, so an Fp2 product reduces each output coefficient once
-// (2 reductions per 3 products instead of 3) and its additions run on the
-// unreduced halves without conditional subtractions.
-// acc(64) + hi(32) += x: one v_mad_u64_u32 with the inline constant 1.
-__device__ __forceinline__ void dx_add32(uint64_t &acc, uint32_t &hi, uint32_t x) {
-  uint64_t cy, unused;
-  asm("v_mad_u64_u32 %0, %2, %4, 1, %0\n\t"
-      "v_addc_co_u32_e64 %1, %3, %1, 0, %2"
-      : "+v"(acc), "+v"(hi), "=&s"(cy), "=&s"(unused)
-      : "v"(x));
-}
-
-// t[16] = a * b for a, b < 2^255 (product scanning, no reduction).
-__device__ __forceinline__ void fmul_wide(const uint32_t *a, const uint32_t *b, uint32_t *t) {
-  MacQ q;
-#pragma unroll
-  for (int i = 0; i < 15; i++) {
-#pragma unroll
-    for (int j = (i > 7 ? i - 7 : 0); j <= (i < 7 ? i : 7); j++) q.push(a[j], b[i - j]);
-    t[i] = q.next_column();
+    for (int j = i - 8; j < 9; j++) {
+      acc += (uint64_t)A[j] * B[i - j];
+      if (TWO) acc += (uint64_t)C[j] * D[i - j];
+      acc += (uint64_t)m[j] * MP::P[i - j];
+    }
+    u[i - 9] = (uint32_t)acc & M29;
+    acc >>= 29;
   }
-  t[15] = (uint32_t)q.acc;
+  u[8] = (uint32_t)acc;
 }
 
-// Montgomery reduction t * 2^-256 mod MOD of a 512-bit t < MOD * 2^256
-// (product scanning over the m_i * MOD columns) -> result < MOD.
+// Nine limbs (u[0..7] < 2^29, u[8] < 2^24) of a value below 2 MOD -> canonical
+// 8 x 32.  Word k starts at bit s = 32 k - 29 j of limb j = 32 k / 29; s is
+// one of 0, 3, .., 21, so both shift counts (s and 29 - s) stay in [0, 29].
 template <class PR>
-__device__ __forceinline__ FieldT<PR> fred_wide(const uint32_t *t) {
-  uint32_t m[8], u[8];
-  MacQ q;
-#pragma unroll
-  for (int i = 0; i < 8; i++) {
-#pragma unroll
-    for (int j = 0; j < i; j++) q.push_mod(m[j], PR::MOD[i - j]);
-    q.flush();
-    dx_add32(q.acc, q.hi, t[i]);
-    m[i] = (uint32_t)q.acc * PR::INV;
-    q.push_mod(m[i], PR::MOD[0]);
-    (void)q.next_column();
-  }
-#pragma unroll
-  for (int i = 8; i < 16; i++) {
-#pragma unroll
-    for (int j = i - 7; j < 8; j++) q.push_mod(m[j], PR::MOD[i - j]);
-    q.flush();
-    dx_add32(q.acc, q.hi, t[i]);
-    u[i - 8] = q.next_column();
-  }
-  // (t + m MOD) / 2^256 < 2 MOD: one conditional subtraction
-  uint32_t s[8], br = 0;
-#pragma unroll
-  for (int i = 0; i < 8; i++) s[i] = subb32(u[i], PR::MOD[i], br);
-  const bool keep = ((uint32_t)q.acc == 0) && br;
-  FieldT<PR> r;
-#pragma unroll
-  for (int i = 0; i < 8; i++) r.v[i] = keep ? u[i] : s[i];
-  return r;
-}
-#else
-// Montgomery multiplication, no-carry CIOS. a*b*2^-256 mod MOD.
-template <class PR>
-DX_MUL FieldT<PR> fmul(const FieldT<PR> &a, const FieldT<PR> &b) {
+DX_HD FieldT<PR> pack(const uint32_t *u) {
   uint32_t t[8];
 #pragma unroll
-  for (int j = 0; j < 8; j++) t[j] = 0;
-#pragma unroll
-  for (int i = 0; i < 8; i++) {
-    const uint32_t bi = b.v[i];
-    uint64_t x = (uint64_t)a.v[0] * bi + t[0];
-    uint32_t A = (uint32_t)(x >> 32);
-    uint32_t t0 = (uint32_t)x;
-    uint32_t m = t0 * PR::INV;
-    uint64_t y = (uint64_t)m * PR::MOD[0] + t0;
-    uint32_t C = (uint32_t)(y >> 32);
-#pragma unroll
-    for (int j = 1; j < 8; j++) {
-      x = (uint64_t)a.v[j] * bi + t[j] + A;
-      A = (uint32_t)(x >> 32);
-      y = (uint64_t)m * PR::MOD[j] + (uint32_t)x + C;
-      C = (uint32_t)(y >> 32);
-      t[j - 1] = (uint32_t)y;
-    }
-    t[7] = C + A;
+  for (int k = 0; k < 8; k++) {
+    const int j = (32 * k) / 29, s = 32 * k - 29 * j;
+    t[k] = (u[j] >> s) | (u[j + 1] << (29 - s));
   }
   cond_sub_mod<PR>(t);
   FieldT<PR> r;
@@ -372,7 +250,54 @@ DX_MUL FieldT<PR> fmul(const FieldT<PR> &a, const FieldT<PR> &b) {
   for (int i = 0; i < 8; i++) r.v[i] = t[i];
   return r;
 }
-#endif
+}  // namespace l29
+
+// Montgomery product a b 2^-256 mod MOD, canonical.  In: a < 2^256, b < MOD
+// (or the other way round).  Before the conditional subtraction the value is
+// below 2 MOD (below 1.2 MOD for a, b < MOD).
+template <class PR>
+DX_MUL FieldT<PR> fmul29(const FieldT<PR> &a, const FieldT<PR> &b) {
+  uint32_t A[9], B[9], u[9];
+  l29::unpack<5>(a.v, A);
+  l29::unpack<0>(b.v, B);
+  l29::redc_cols<PR, false>(A, B, A, B, u);
+  return l29::pack<PR>(u);
+}
+
+// Sum of two products (a b + c d) 2^-256 mod MOD, canonical, in one reduced
+// column chain.  In: a, b, c, d <= MOD.  Before the conditional subtraction
+// the value is below MOD (1 + 2 MOD / 2^256) < 1.4 MOD.
+template <class PR>
+DX_MUL FieldT<PR> fmul2_29(const FieldT<PR> &a, const FieldT<PR> &b, const FieldT<PR> &c, const FieldT<PR> &d) {
+  uint32_t A[9], B[9], C[9], D[9], u[9];
+  l29::unpack<5>(a.v, A);
+  l29::unpack<0>(b.v, B);
+  l29::unpack<5>(c.v, C);
+  l29::unpack<0>(d.v, D);
+  l29::redc_cols<PR, true>(A, B, C, D, u);
+  return l29::pack<PR>(u);
+}
+
+// MOD - a for a < MOD: in (0, MOD], a valid operand of the products above
+// (not canonical for a = 0).
+template <class PR>
+DX_HD FieldT<PR> mod_minus(const FieldT<PR> &a) {
+  FieldT<PR> r;
+  uint32_t br = 0;
+#pragma unroll
+  for (int i = 0; i < 8; i++) r.v[i] = subb32(PR::MOD[i], a.v[i], br);
+  return r;
+}
+
+template <class PR>
+DX_HD FieldT<PR> fmul(const FieldT<PR> &a, const FieldT<PR> &b) {
+  return fmul29(a, b);
+}
+// (a b + c d) 2^-256 mod MOD for a, b, c, d <= MOD
+template <class PR>
+DX_HD FieldT<PR> fmul2(const FieldT<PR> &a, const FieldT<PR> &b, const FieldT<PR> &c, const FieldT<PR> &d) {
+  return fmul2_29(a, b, c, d);
+}
 
 template <class PR>
 DX_HD FieldT<PR> fsqr(const FieldT<PR> &a) {

@@ -16,6 +16,41 @@ int dx_fp_from_mont(int on_gpu, void *stream, const uint32_t *in, uint32_t *out,
   return run(on_gpu, stream, n, op, false, "fp_from_mont");
 }
 
+// Elementwise probe of the field core, for the tests alone (raw Montgomery
+// products of the given limbs, no domain conversion).  opc: 0 Fp mul, 1 Fp sqr
+// (a), 2 Fr mul, 3 Fp2 mul, 4 Fp2 sqr (a), 5 Fp2 (a) * Fp (b).  Rows are 8
+// words per Fp / Fr and 16 per Fp2.
+int dx_field_probe(int on_gpu, void *stream, int opc, const uint32_t *a, const uint32_t *b, uint32_t *out,
+                   int64_t n) {
+  switch (opc) {
+    case 0: {
+      auto op = [=] __host__ __device__(int64_t i) { at<Fp>(out, i) = fmul(at<Fp>(a, i), at<Fp>(b, i)); };
+      return run(on_gpu, stream, n, op, false, "probe_fp_mul");
+    }
+    case 1: {
+      auto op = [=] __host__ __device__(int64_t i) { at<Fp>(out, i) = fsqr(at<Fp>(a, i)); };
+      return run(on_gpu, stream, n, op, false, "probe_fp_sqr");
+    }
+    case 2: {
+      auto op = [=] __host__ __device__(int64_t i) { at<Fr>(out, i) = fmul(at<Fr>(a, i), at<Fr>(b, i)); };
+      return run(on_gpu, stream, n, op, false, "probe_fr_mul");
+    }
+    case 3: {
+      auto op = [=] __host__ __device__(int64_t i) { at<Fp2>(out, i) = mul(at<Fp2>(a, i), at<Fp2>(b, i)); };
+      return run(on_gpu, stream, n, op, false, "probe_fp2_mul");
+    }
+    case 4: {
+      auto op = [=] __host__ __device__(int64_t i) { at<Fp2>(out, i) = sqr(at<Fp2>(a, i)); };
+      return run(on_gpu, stream, n, op, false, "probe_fp2_sqr");
+    }
+    case 5: {
+      auto op = [=] __host__ __device__(int64_t i) { at<Fp2>(out, i) = mul_fp(at<Fp2>(a, i), at<Fp>(b, i)); };
+      return run(on_gpu, stream, n, op, false, "probe_fp2_mul_fp");
+    }
+    default: return -1;
+  }
+}
+
 }  // extern "C"
 
 // Fr arithmetic on canonical scalars. op: 0 add, 1 sub, 2 mul, 3 neg(a), 4 inv(a), 5 reduce(a)

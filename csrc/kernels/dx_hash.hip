@@ -384,6 +384,15 @@ extern "C" int dx_sha256_segments(int on_gpu, void *stream, const int64_t *seg, 
   return run(on_gpu, stream, total, op, false, "sha256_segments");
 }
 
+// for_each_kernel64 with a target of 4 waves per SIMD: the square-root ladder
+// is one long dependent chain per lane, and at the default target of 2 the
+// register allocator settles a few registers above the 128 that 4 waves allow.
+template <class Op>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) hash_to_g1_kernel(int64_t n, Op op) {
+  int64_t i = (int64_t)blockIdx.x * 64 + threadIdx.x;
+  if (i < n) op(i);
+}
+
 // Independent G1 generators h_i (unknown discrete logs) for commitment
 // schemes -- the permutation commitments of the shuffle proof.  For index i:
 // ctr = 0, 1, ...: x = SHA-256(seed || le64(i) || le32(ctr)) (big endian) mod p;
@@ -428,5 +437,12 @@ extern "C" int dx_hash_to_g1(int on_gpu, void *stream, const uint32_t *seed_host
     }
     at<G1A>(out_aff, k) = res;
   };
-  return run(on_gpu, stream, n, op, true, "hash_to_g1");
+  if (n <= 0) return 0;
+  if (!on_gpu) {
+    host_for_each(n, op, 2);
+    return 0;
+  }
+  hipLaunchKernelGGL(hash_to_g1_kernel<decltype(op)>, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, (hipStream_t)stream,
+                     n, op);
+  return check_hip(hipGetLastError(), "hash_to_g1");
 }

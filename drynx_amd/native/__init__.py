@@ -54,6 +54,7 @@ _L = ctypes.c_int64
 _SIGS = {
     "dx_fp_to_mont": [_I, _P, _P, _P, _L],
     "dx_fp_from_mont": [_I, _P, _P, _P, _L],
+    "dx_field_probe": [_I, _P, _I, _P, _P, _P, _L],
     "dx_fr_arith": [_I, _P, _I, _P, _P, _P, _L, _L],
     "dx_fr_dot_chunks": [_I, _P, _P, _P, _I, _P, _L, _L, _L],
     "dx_fr_seg_sum": [_I, _P, _P, _P, _P, _L],
@@ -261,6 +262,27 @@ def fp_from_mont(x: torch.Tensor) -> torch.Tensor:
     out = torch.empty_like(x)
     g, s = _ctx(x)
     _call("dx_fp_from_mont", g, s, _ptr(x), _ptr(out), _rows(x, 8))
+    return out
+
+
+PROBE_FP_MUL, PROBE_FP_SQR, PROBE_FR_MUL, PROBE_FP2_MUL, PROBE_FP2_SQR, PROBE_FP2_MUL_FP = range(6)
+
+
+def field_probe(opc: int, a: torch.Tensor, b: torch.Tensor | None = None) -> torch.Tensor:
+    """Raw Montgomery products of the field core, row by row (tests only):
+    out = a * b * 2^-256 mod the modulus on the limbs as given.  Rows are 8
+    words (Fp, Fr) or 16 (Fp2); PROBE_FP2_MUL_FP takes a [n, 16] and b [n, 8];
+    the squarings ignore b."""
+    wa = 16 if opc >= PROBE_FP2_MUL else 8
+    wb = 8 if opc == PROBE_FP2_MUL_FP else wa
+    n = _rows(a, wa)
+    if opc in (PROBE_FP_SQR, PROBE_FP2_SQR):
+        b = a
+    else:
+        assert _rows(b, wb) == n, (a.shape, b.shape)
+    out = torch.empty_like(a)
+    g, s = _ctx(a, b)
+    _call("dx_field_probe", g, s, opc, _ptr(a), _ptr(b), _ptr(out), n)
     return out
 
 

@@ -1,14 +1,17 @@
 // Microbenchmark: issue rates of the instructions a BN254 field multiplication
-// can be built from on gfx950, and the production Montgomery multiply
-// (csrc/bn254/field.h fmul) itself -- to price a 52-bit-limb FP64 FMA field
-// (Emmart-Zheng-Weems style: exact products split by two FMAs) against the
-// 32-bit-limb integer path.  Every kernel runs 8 independent chains per lane
-// (enough ILP to measure issue rate, not latency) over a full-chip grid.
+// can be built from on gfx950, and the Montgomery products themselves: the
+// production 9 x 29-bit-limb core (csrc/bn254/field.h fmul, tower.h Fp2 mul)
+// and the 8 x 32-bit inline-asm core it replaced (field_mac32.h), side by side
+// in one binary -- and to price a 52-bit-limb FP64 FMA field (Emmart-Zheng-Weems
+// style: exact products split by two FMAs) against the integer paths.  Every
+// instruction kernel runs 8 independent chains per lane (enough ILP to measure
+// issue rate, not latency) over a full-chip grid.
 //
 // Build: hipcc -O3 -std=c++17 --offload-arch=gfx950 -I csrc tools/fp_rate_bench.hip -o tools/bin/fp_rate_bench
 // Run:   tools/bin/fp_rate_bench
 #define DX_NI __host__ __device__ __forceinline__
 #include "kernels/common.h"
+#include "bn254/field_mac32.h"
 
 #include <chrono>
 #include <cstdio>
@@ -89,20 +92,60 @@ __global__ void __launch_bounds__(kWG) fma_f32_kernel(float *out, int iters) {
   out[i] = s;
 }
 
-// production Montgomery multiply: 4 independent chains (each an 8-limb Fp)
+// the asm core exists in the device pass only
+__device__ __forceinline__ Fp old_fmul(const Fp &a, const Fp &b) {
+#ifdef __HIP_DEVICE_COMPILE__
+  return fmul_mac32(a, b);
+#else
+  return a;
+#endif
+}
+__device__ __forceinline__ Fp2 old_fp2_mul(const Fp2 &a, const Fp2 &b) {
+  Fp2 r = a;
+#ifdef __HIP_DEVICE_COMPILE__
+  fp2_mul_mac32(a.c0, a.c1, b.c0, b.c1, r.c0, r.c1);
+#endif
+  return r;
+}
+
+// Montgomery multiply, 4 independent chains (each an 8-limb Fp); OLD selects
+// the 8 x 32-bit asm core, otherwise the production 9 x 29-bit one
+template <bool OLD>
 __global__ void __launch_bounds__(kWG) DX_OCC fmul_kernel(const uint32_t *in, uint32_t *out, int iters) {
   const int64_t i = (int64_t)blockIdx.x * kWG + threadIdx.x;
   Fp x[4], y = at<Fp>(in, 4);
 #pragma unroll
-  for (int c = 0; c < 4; c++) x[c] = at<Fp>(in, c);
+  for (int c = 0; c < 4; c++) {
+    x[c] = at<Fp>(in, c);
+    x[c].v[0] += (uint32_t)i;  // per-lane values: uniform ones let the compiler move the plain-C++ core to the SALU
+  }
   for (int it = 0; it < iters; it++) {
 #pragma unroll
-    for (int c = 0; c < 4; c++) x[c] = fmul(x[c], y);
+    for (int c = 0; c < 4; c++) x[c] = OLD ? old_fmul(x[c], y) : fmul29(x[c], y);
   }
   Fp s = x[0];
 #pragma unroll
   for (int c = 1; c < 4; c++) s = fadd(s, x[c]);
   at<Fp>(out, i) = s;
+}
+
+// Fp2 product, 2 independent chains
+template <bool OLD>
+__global__ void __launch_bounds__(kWG) DX_OCC fp2_mul_kernel(const uint32_t *in, uint32_t *out, int iters) {
+  const int64_t i = (int64_t)blockIdx.x * kWG + threadIdx.x;
+  Fp2 x[2] = {at<Fp2>(in, 0), at<Fp2>(in, 1)};
+  const Fp2 y = {at<Fp>(in, 4), at<Fp>(in, 3)};
+  x[0].c0.v[0] += (uint32_t)i;  // per-lane values, as above
+  x[0].c1.v[0] ^= (uint32_t)i;
+  x[1].c0.v[0] ^= (uint32_t)i;
+  x[1].c1.v[0] += (uint32_t)i;
+  for (int it = 0; it < iters; it++) {
+#pragma unroll
+    for (int c = 0; c < 2; c++) {
+      x[c] = OLD ? old_fp2_mul(x[c], y) : mul(x[c], y);
+    }
+  }
+  at<Fp2>(out, i) = add(x[0], x[1]);
 }
 
 template <class F>
@@ -148,9 +191,22 @@ int main() {
          ops / (ms * 1e-3) / cus / (prop.clockRate * 1e3));
   const int fiters = 512;
   const double fops = (double)n * fiters * 4;
-  ms = time_ms([&] { hipLaunchKernelGGL(fmul_kernel, dim3(blocks), dim3(kWG), 0, 0, in, (uint32_t *)buf, fiters); });
-  printf("Fp fmul (field.h)      : %8.3f ms  %8.2f G fmul/s  %6.3f fmul/clk/CU\n", ms, fops / ms / 1e6,
-         fops / (ms * 1e-3) / cus / (prop.clockRate * 1e3));
+  const double f2ops = (double)n * (fiters / 2) * 2;
+  // old and new cores alternate, three rounds: a primitive is adopted only if it wins every round
+  for (int round = 0; round < 3; round++) {
+    ms = time_ms([&] { hipLaunchKernelGGL(fmul_kernel<true>, dim3(blocks), dim3(kWG), 0, 0, in, (uint32_t *)buf, fiters); });
+    printf("Fp fmul  8x32 asm  (field_mac32.h): %8.3f ms  %8.2f G fmul/s  %6.3f fmul/clk/CU\n", ms, fops / ms / 1e6,
+           fops / (ms * 1e-3) / cus / (prop.clockRate * 1e3));
+    ms = time_ms([&] { hipLaunchKernelGGL(fmul_kernel<false>, dim3(blocks), dim3(kWG), 0, 0, in, (uint32_t *)buf, fiters); });
+    printf("Fp fmul  9x29      (field.h)      : %8.3f ms  %8.2f G fmul/s  %6.3f fmul/clk/CU\n", ms, fops / ms / 1e6,
+           fops / (ms * 1e-3) / cus / (prop.clockRate * 1e3));
+    ms = time_ms(
+        [&] { hipLaunchKernelGGL(fp2_mul_kernel<true>, dim3(blocks), dim3(kWG), 0, 0, in, (uint32_t *)buf, fiters / 2); });
+    printf("Fp2 mul  8x32 asm  (field_mac32.h): %8.3f ms  %8.2f G mul/s\n", ms, f2ops / ms / 1e6);
+    ms = time_ms(
+        [&] { hipLaunchKernelGGL(fp2_mul_kernel<false>, dim3(blocks), dim3(kWG), 0, 0, in, (uint32_t *)buf, fiters / 2); });
+    printf("Fp2 mul  9x29      (tower.h)      : %8.3f ms  %8.2f G mul/s\n", ms, f2ops / ms / 1e6);
+  }
   (void)hipFree(buf);
   (void)hipFree(in);
   return 0;
