@@ -156,6 +156,12 @@ DX_HD bool on_curve(const G2A &a) {
 DX_HD G1A g1_generator() { return {Fp::from_limbs(Curve::G1X), Fp::from_limbs(Curve::G1Y)}; }
 DX_HD G2A g2_generator() { return {Fp2::from_limbs(Curve::G2X), Fp2::from_limbs(Curve::G2Y)}; }
 
+// psi (untwist-Frobenius-twist, eigenvalue 6u^2 on G2) on Jacobian coordinates:
+// (X, Y, Z) -> (conj(X) twx, conj(Y) twy, conj(Z)).
+DX_HD G2J psi(const G2J &q) {
+  return {mul(conj(q.x), Fp2::from_limbs(Frob::TWX1)), mul(conj(q.y), Fp2::from_limbs(Frob::TWY1)), conj(q.z)};
+}
+
 DX_HD bool scalar_is_zero(const uint32_t *k) {
   uint32_t acc = 0;
 #pragma unroll

@@ -1,14 +1,19 @@
 // GLS-2 fixed-base tables with SIGNED 8-bit windows (prover table mode 7;
 // K6/K7 of the range-proof prover, lib/range/range_proof.go:452-469).
 //
-// Same decomposition as dx_gls.hip: k = k0 + k1 lambda2 (lambda2 = 6u^2, the
-// eigenvalue of psi on G2 and of the Frobenius on GT), k0, k1 < 2^128.  Each
+// The prover's per-item work is V = v A_phi (G2) and e(B, A_phi)^(-s v) (GT)
+// with per-signature bases.  Both groups carry an endomorphism with eigenvalue
+// lambda2 = 6u^2 = p (mod r), a ~127-bit number: psi on G2 (curve.h) and the
+// Frobenius x -> x^p on GT.  Any scalar k < r splits as k = k0 + k1 lambda2
+// with k0 < lambda2 and k1 < 2^128 by one long division (no lattice: lambda2 ~
+// sqrt r), so k Q = k0 Q + psi(k1 Q) and x^k = x^k0 * frob(x^k1): two
+// fixed-base evaluations over 128-bit exponents from ONE table per base.  Each
 // half is recoded LSB-first into 17 signed digits in [-127, 128] (a byte plus
 // the carry of the previous window), so one table per base holds
 // d 2^(8w) Q for d = 1..128, w < 17 (2176 entries: 272 KiB on G2, 408 KiB on
 // GT), and a negative digit uses the negated entry -- y -> -y on G2,
 // beta -> -beta on GT.  An evaluation costs 34 mixed additions / GT steps
-// instead of the 44 of the 6-bit unsigned layout.  For the reference's random
+// instead of the 64 of the 4-bit 256-bit comb.  For the reference's random
 // per-CN, per-column keys (99,360 points for a SPECTF-shaped query) the tables
 // take ~70 GB of the 288 GB of HBM.
 //
@@ -66,10 +71,6 @@ DX_HD int sdigit(const uint32_t *k5, int w, uint32_t &carry) {
   return carry ? (int)v - 256 : (int)v;
 }
 
-DX_HD G2J psi_j(const G2J &q) {
-  return {mul(conj(q.x), Fp2::from_limbs(Frob::TWX1)), mul(conj(q.y), Fp2::from_limbs(Frob::TWY1)), conj(q.z)};
-}
-
 DX_HD void g2_half(G2J &a, const G2A *T, const uint32_t *k5) {
   uint32_t c = 0;
   for (int w = 0; w < kWin; w++) {
@@ -87,7 +88,7 @@ DX_HD G2J g2_gls8_eval(const G2A *T, const uint32_t *k) {
   split_lambda2(k, k0, k1);
   G2J a = G2J::inf();
   g2_half(a, T, k1);
-  a = psi_j(a);
+  a = psi(a);
   g2_half(a, T, k0);
   return a;
 }

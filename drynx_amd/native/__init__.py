@@ -148,12 +148,6 @@ _SIGS = {
     "dx_rp_accum_n": [_P, _P, _P, _P, _P, _L, _L, _I, _I],
     "dx_ufold_coop_raw": [_P, _P, _P, _P, _P, _L, _L, _L],
     "dx_gt_frob8": [_I, _P, _P, _P, _L],
-    "dx_gls6_entries": [],
-    "dx_g2_gls6_table": [_I, _P, _P, _P, _P, _L],
-    "dx_g2_gls6_mul": [_I, _P, _P, _P, _P, _P, _L],
-    "dx_gt_gls6_table": [_I, _P, _P, _P, _P, _L],
-    "dx_gt_gls6_pow": [_I, _P, _P, _P, _P, _P, _L],
-    "dx_rp_prove_a_gls6": [_I, _P, _P, _P, _P, _P, _P, _P, _L, _I, _I],
     "dx_g2_joint_table": [_I, _P, _P, _P, _L],
     "dx_g2_joint_table_signed": [_I, _P, _P, _P, _P, _L],
     "dx_rp_u_group": [_I, _P, _P, _P, _P, _P, _P, _P, _L, _I, _L, _I, _I, _L, _P, _P],
@@ -621,17 +615,25 @@ def g2_fb_mul(tables: torch.Tensor, scalars: torch.Tensor, tab_idx: torch.Tensor
 FB4_ENTRIES = 960  # 64 windows x 15 non-zero digits
 
 
-def g2_fb4_table(base_aff: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
-    """4-bit comb table(s) [n_bases*960, 32] (120 KiB per base).  ``out``: a
-    preallocated slice of a larger table tensor to fill in place."""
-    bases = base_aff.contiguous().view(-1, 32)
+def _window_table(sym: str, bases: torch.Tensor, width: int, entries: int, windows: int, work_width: int,
+                  out: torch.Tensor | None) -> torch.Tensor:
+    """Windowed fixed-base table(s) [n_bases*entries, width] by the native
+    builder ``sym`` (``windows`` work rows of ``work_width`` words per base).
+    ``out``: a preallocated slice of a larger table tensor to fill in place."""
+    assert bases.dtype == torch.int32
+    bases = bases.contiguous().view(-1, width)
     nb = bases.shape[0]
-    table = out if out is not None else torch.empty((nb * FB4_ENTRIES, 32), dtype=torch.int32, device=bases.device)
-    assert table.shape == (nb * FB4_ENTRIES, 32) and table.is_contiguous()
-    work = torch.empty((nb * 64, 48), dtype=torch.int32, device=bases.device)
+    table = out if out is not None else torch.empty((nb * entries, width), dtype=torch.int32, device=bases.device)
+    assert table.shape == (nb * entries, width) and table.is_contiguous()
+    work = torch.empty((nb * windows, work_width), dtype=torch.int32, device=bases.device)
     g, s = _ctx(bases, table)
-    _call("dx_g2_fb4_table", g, s, _ptr(bases), _ptr(work), _ptr(table), nb)
+    _call(sym, g, s, _ptr(bases), _ptr(work), _ptr(table), nb)
     return table
+
+
+def g2_fb4_table(base_aff: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+    """4-bit comb table(s) [n_bases*960, 32] (120 KiB per base)."""
+    return _window_table("dx_g2_fb4_table", base_aff, 32, FB4_ENTRIES, 64, 48, out)
 
 
 def g2_fb4_mul(tables: torch.Tensor, scalars: torch.Tensor, tab_idx: torch.Tensor | None = None) -> torch.Tensor:
@@ -642,63 +644,12 @@ def g2_fb4_mul(tables: torch.Tensor, scalars: torch.Tensor, tab_idx: torch.Tenso
     return out
 
 
-GLS6_ENTRIES = 1386  # 22 six-bit windows x 63 non-zero digits (csrc/kernels/dx_gls.hip)
-
-
-def g2_gls6_table(base_aff: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
-    """GLS-2 6-bit fixed-base table(s) [n_bases*1386, 32] (177 KiB per base)."""
-    bases = base_aff.contiguous().view(-1, 32)
-    nb = bases.shape[0]
-    table = out if out is not None else torch.empty((nb * GLS6_ENTRIES, 32), dtype=torch.int32, device=bases.device)
-    assert table.shape == (nb * GLS6_ENTRIES, 32) and table.is_contiguous()
-    work = torch.empty((nb * 22, 48), dtype=torch.int32, device=bases.device)
-    g, s = _ctx(bases, table)
-    _call("dx_g2_gls6_table", g, s, _ptr(bases), _ptr(work), _ptr(table), nb)
-    return table
-
-
-def g2_gls6_mul(tables: torch.Tensor, scalars: torch.Tensor, tab_idx: torch.Tensor | None = None) -> torch.Tensor:
-    """k * A (affine) with k = k0 + k1 lambda2, psi(k1 A) + k0 A from one table."""
-    n = _rows(scalars, 8)
-    out = torch.empty((n, 32), dtype=torch.int32, device=scalars.device)
-    g, s = _ctx(tables, scalars, tab_idx)
-    _call("dx_g2_gls6_mul", g, s, _ptr(tables), _ptr(tab_idx), _ptr(scalars), _ptr(out), n)
-    return out
-
-
-def gt_gls6_table(bases: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
-    """GLS-2 6-bit fixed-base table(s) [n_bases*1386, 96] of GT elements (532 KiB per base)."""
-    bases = bases.contiguous()
-    nb = _rows(bases, 96)
-    table = out if out is not None else torch.empty((nb * GLS6_ENTRIES, 96), dtype=torch.int32, device=bases.device)
-    assert table.shape == (nb * GLS6_ENTRIES, 96) and table.is_contiguous()
-    work = torch.empty((nb * 22, 96), dtype=torch.int32, device=bases.device)
-    g, s = _ctx(bases, table)
-    _call("dx_gt_gls6_table", g, s, _ptr(bases), _ptr(work), _ptr(table), nb)
-    return table
-
-
-def gt_gls6_pow(tables: torch.Tensor, scalars: torch.Tensor, tab_idx: torch.Tensor | None = None) -> torch.Tensor:
-    n = _rows(scalars, 8)
-    out = torch.empty((n, 96), dtype=torch.int32, device=scalars.device)
-    g, s = _ctx(tables, scalars, tab_idx)
-    _call("dx_gt_gls6_pow", g, s, _ptr(tables), _ptr(tab_idx), _ptr(scalars), _ptr(out), n)
-    return out
-
-
 GLS8_ENTRIES = 2176  # 17 signed byte windows x 128 digits (csrc/kernels/dx_gls8.hip)
 
 
 def g2_gls8_table(base_aff: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
     """GLS-2 signed 8-bit fixed-base table(s) [n_bases*2176, 32] (272 KiB per base)."""
-    bases = base_aff.contiguous().view(-1, 32)
-    nb = bases.shape[0]
-    table = out if out is not None else torch.empty((nb * GLS8_ENTRIES, 32), dtype=torch.int32, device=bases.device)
-    assert table.shape == (nb * GLS8_ENTRIES, 32) and table.is_contiguous()
-    work = torch.empty((nb * 17, 48), dtype=torch.int32, device=bases.device)
-    g, s = _ctx(bases, table)
-    _call("dx_g2_gls8_table", g, s, _ptr(bases), _ptr(work), _ptr(table), nb)
-    return table
+    return _window_table("dx_g2_gls8_table", base_aff, 32, GLS8_ENTRIES, 17, 48, out)
 
 
 def gt_gls8_table(bases: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
@@ -1000,14 +951,7 @@ def gt_fb_pow(tables: torch.Tensor, scalars: torch.Tensor, tab_idx: torch.Tensor
 
 def gt_fb4_table(bases: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
     """4-bit comb table(s) [n_bases*960, 96] (360 KiB per base)."""
-    bases = bases.contiguous()
-    nb = _rows(bases, 96)
-    table = out if out is not None else torch.empty((nb * FB4_ENTRIES, 96), dtype=torch.int32, device=bases.device)
-    assert table.shape == (nb * FB4_ENTRIES, 96) and table.is_contiguous()
-    work = torch.empty((nb * 64, 96), dtype=torch.int32, device=bases.device)
-    g, s = _ctx(bases, table)
-    _call("dx_gt_fb4_table", g, s, _ptr(bases), _ptr(work), _ptr(table), nb)
-    return table
+    return _window_table("dx_gt_fb4_table", bases, 96, FB4_ENTRIES, 64, 96, out)
 
 
 def gt_fb4_pow(tables: torch.Tensor, scalars: torch.Tensor, tab_idx: torch.Tensor | None = None) -> torch.Tensor:
@@ -1482,9 +1426,8 @@ def rp_prove_a(negsB_aff, V_aff, t_sc, gt_table, S: int, L: int) -> torch.Tensor
 
 def rp_prove_a_tab(gphi_tables, tab_idx, e_sc, t_sc, gt_table, S: int, L: int, wbits: int = 8) -> torch.Tensor:
     """wbits = 8: gphi_tables in the 8-bit comb layout; 4: the 4-bit layout
-    (gt_fb4_table); 6: the GLS-2 6-bit layout (gt_gls6_table); 7: the GLS-2
-    signed 8-bit layout (gt_gls8_table)."""
-    assert wbits in (4, 6, 7, 8)
+    (gt_fb4_table); 7: the GLS-2 signed 8-bit layout (gt_gls8_table)."""
+    assert wbits in (4, 7, 8)
     n = _rows(e_sc, 8)
     out = torch.empty((n, 96), dtype=torch.int32, device=e_sc.device)
     g, s = _ctx(gphi_tables, tab_idx, e_sc, t_sc, gt_table)
@@ -1494,10 +1437,6 @@ def rp_prove_a_tab(gphi_tables, tab_idx, e_sc, t_sc, gt_table, S: int, L: int, w
         tmp = torch.empty_like(out) if g else None                             # the finish pass's prefixes and norms
         _call("dx_rp_prove_a_gls8", g, s, _ptr(gphi_tables), _ptr(tab_idx), _ptr(e_sc), _ptr(t_sc),
               _ptr(t16 if t16 is not None else gt_table), _ptr(out), n, S, L, int(t16 is not None), _ptr(tmp))
-        return out
-    if wbits == 6:
-        _call("dx_rp_prove_a_gls6", g, s, _ptr(gphi_tables), _ptr(tab_idx), _ptr(e_sc), _ptr(t_sc), _ptr(gt_table),
-              _ptr(out), n, S, L)
         return out
     _call("dx_rp_prove_a_tab", g, s, _ptr(gphi_tables), _ptr(tab_idx), _ptr(e_sc), _ptr(t_sc), _ptr(gt_table),
           _ptr(out), n, S, L, wbits)

@@ -12,7 +12,9 @@ Reference: lib/range/range_proof.go
 MI355X design (all lists of proofs are processed as ONE batch on the device):
   prove : table-driven -- V = v A_phi from G2 comb / GLS tables of the
           signature points and a = e(B, A_phi)^{-s v} gT^t from GT tables
-          (``SigMaterial.table_mode``: no pairing per item); without tables
+          (one of ``PROVER_LAYOUTS``, chosen by ``SigMaterial.table_mode``:
+          8-bit combs, GLS-2 signed 8-bit windows or 4-bit combs, whichever
+          fits its HBM budget first; no pairing per item); without tables
           (too many distinct points for HBM) a_ij = FE(ML(-s_j B, V_ij)) *
           gT^{t_j} (fused kernel dx_rp_prove_a).  D = (sum u^j s_j) B +
           (sum m_j) P by two fixed-base mults; all Fr arithmetic on device.
@@ -38,6 +40,7 @@ import math
 import os
 import threading
 from dataclasses import dataclass
+from typing import Callable
 
 import numpy as np
 import torch
@@ -112,6 +115,41 @@ def init_range_proof_signatures(us: list, device="cpu") -> list:
 def init_range_proof_signature_deterministic(u: int, device="cpu") -> PublishSignatureBytes:
     """InitRangeProofSignatureDeterministic: x = 12 (range_proof.go:249)."""
     return init_range_proof_signature(u, 12, device)
+
+
+@dataclass(frozen=True)
+class ProverLayout:
+    """One layout of the prover's fixed-base tables of a signature point A:
+    a G2 table for V = v A and a GT table for e(B, A)^e."""
+    mode: int        # the DRYNX_PROVER_TABLE_BITS value, ``wbits`` of nt.rp_prove_a_tab, the benches' prover_table_mode
+    entries: int     # table rows per distinct point
+    gt_words: int    # int32 words per GT row: 96 (an Fp12 element) or 48 (its torus image)
+    g2_table: Callable
+    gt_table: Callable
+    g2_mul: Callable
+    budget: str      # the environment variable (MiB) its size is tested against
+    whole_set: bool  # tables of every distinct point of the set up front, or of the points used so far
+
+    @property
+    def bytes_per_point(self) -> int:
+        return self.entries * 4 * (32 + self.gt_words)
+
+
+# in order of preference: the first whose tables fit its budget is taken
+PROVER_LAYOUTS = (
+    # 8-bit combs, 32 additions per evaluation, 4 MiB per point: few distinct
+    # points (InitRangeProofSignatureDeterministic)
+    ProverLayout(8, 8192, 96, nt.g2_fb_table, nt.gt_fb_table, nt.g2_fb_mul, "DRYNX_PROVER_TABLE_MB", False),
+    # GLS-2 with signed 8-bit windows, 34 additions, 680 KiB per point: the
+    # reference's random per-CN, per-column keys (99,360 points for a
+    # SPECTF-shaped query with 3 CNs and u = 16: 69.2 GB of HBM)
+    ProverLayout(7, nt.GLS8_ENTRIES, 48, nt.g2_gls8_table, nt.gt_gls8_table, nt.g2_gls8_mul,
+                 "DRYNX_PROVER_TABLE4_MB", True),
+    # 4-bit combs, 64 additions, 480 KiB per point
+    ProverLayout(4, nt.FB4_ENTRIES, 96, nt.g2_fb4_table, nt.gt_fb4_table, nt.g2_fb4_mul,
+                 "DRYNX_PROVER_TABLE4_MB", True),
+)
+LAYOUT_OF_MODE = {lay.mode: lay for lay in PROVER_LAYOUTS}
 
 
 class SigMaterial:
@@ -254,16 +292,10 @@ class SigMaterial:
             self._shard = None
 
     def table_mode(self, device) -> int:
-        """Prover comb-table layout for this signature set on ``device``:
-        8 (8-bit combs, 4 MiB per distinct point: few distinct points, e.g.
-        InitRangeProofSignatureDeterministic), 7 (GLS-2 tables with signed
-        8-bit windows, GT entries as 192-byte torus images, 0.66 MiB per point,
-        34 additions per evaluation: the reference's random per-CN, per-column
-        keys -- 99,360 points for a SPECTF-shaped query with 3 CNs and u = 16,
-        ~70 GB of HBM), 6 (GLS-2
-        with unsigned 6-bit windows, 693 KiB per point, 44 additions), 4 (4-bit
-        combs, 480 KiB per point, 64 additions) or 0 (no
-        tables: variable-base G2 + one pairing per item).  Budgets:
+        """Prover table layout for this signature set on ``device``: the mode
+        of the first of ``PROVER_LAYOUTS`` whose tables of the set's distinct
+        points fit its budget, or 0 (no tables: variable-base G2 + one pairing
+        per item).  ``DRYNX_PROVER_TABLE_BITS`` forces a mode.  Budgets:
         ``DRYNX_PROVER_TABLE_MB`` (8-bit, default 8 GiB on a GPU / 96 MiB on the
         host) and ``DRYNX_PROVER_TABLE4_MB`` (GLS / 4-bit layouts, default: the
         free HBM minus the verifier's reserve ``DRYNX_VERIFY_RESERVE_GB`` = 48,
@@ -275,7 +307,11 @@ class SigMaterial:
         if key in self._ptab:
             return self._ptab[key]
         n = self.n_distinct
+        modes = [lay.mode for lay in PROVER_LAYOUTS] + [0]  # most generous first
         forced = os.environ.get("DRYNX_PROVER_TABLE_BITS")
+        if forced is not None and forced not in map(str, modes):
+            raise ValueError(f"DRYNX_PROVER_TABLE_BITS={forced!r}: accepted values are "
+                             f"{', '.join(map(str, sorted(modes)))}")
         b8 = int(os.environ.get("DRYNX_PROVER_TABLE_MB", 8192 if dev.type == "cuda" else 96)) << 20
         if "DRYNX_PROVER_TABLE4_MB" in os.environ:
             b4 = int(os.environ["DRYNX_PROVER_TABLE4_MB"]) << 20
@@ -289,23 +325,15 @@ class SigMaterial:
             b4 = max(0, min(int(0.85 * free), free - reserve))
         else:
             b4 = 64 << 20
-        if forced in ("0", "4", "6", "7", "8"):
+        budget = {"DRYNX_PROVER_TABLE_MB": b8, "DRYNX_PROVER_TABLE4_MB": b4}
+        if forced is not None:
             mode = int(forced)
-        elif n * (4 << 20) <= b8:
-            mode = 8
-        elif n * nt.GLS8_ENTRIES * (128 + 192) <= b4:
-            mode = 7
-        elif n * nt.GLS6_ENTRIES * (128 + 384) <= b4:
-            mode = 6
-        elif n * nt.FB4_ENTRIES * (128 + 384) <= b4:
-            mode = 4
         else:
-            mode = 0
+            mode = next((lay.mode for lay in PROVER_LAYOUTS if n * lay.bytes_per_point <= budget[lay.budget]), 0)
         shard = getattr(self, "_shard", None)
         if shard is not None and forced is None:
             # sharded builds need ONE layout on every rank: the most compact one any rank chose
-            order = [8, 7, 6, 4, 0]
-            mode = max(shard.all_gather_object(mode), key=order.index)
+            mode = max(shard.all_gather_object(mode), key=modes.index)
         self._ptab[key] = mode
         return mode
 
@@ -351,18 +379,18 @@ class SigMaterial:
         return self._n_distinct
 
     def _prover_tables4(self, dev, mode: int = 4):
-        """4-bit comb, GLS-2 6-bit (``mode`` 6) or GLS-2 signed 8-bit (7) tables
-        of EVERY distinct signature point of the set, built once (chunked) and
-        kept in HBM for the set's lifetime; -> (g2, gt, slot of each A index)."""
+        """The tables of a whole-set layout (``mode`` 4 or 7): those of EVERY
+        distinct signature point of the set, built once (chunked) and kept in
+        HBM for the set's lifetime; -> (g2, gt, slot of each A index)."""
         key = (mode, str(dev))
         if key not in self._ptab:
+            lay = LAYOUT_OF_MODE[mode]
+            assert lay.whole_set
             uniq, slot = torch.unique(self.canon, return_inverse=True)
             n = uniq.numel()
-            E, g2_tab, gt_tab = {4: (nt.FB4_ENTRIES, nt.g2_fb4_table, nt.gt_fb4_table),
-                                 6: (nt.GLS6_ENTRIES, nt.g2_gls6_table, nt.gt_gls6_table),
-                                 7: (nt.GLS8_ENTRIES, nt.g2_gls8_table, nt.gt_gls8_table)}[mode]
+            E = lay.entries
             g2 = torch.empty((n * E, 32), dtype=torch.int32, device=dev)
-            gt = torch.empty((n * E, 48 if mode == 7 else 96), dtype=torch.int32, device=dev)  # 7: torus images
+            gt = torch.empty((n * E, lay.gt_words), dtype=torch.int32, device=dev)
             A = self.A.to(dev)
             step = 8192
             shard = getattr(self, "_shard", None)
@@ -374,9 +402,9 @@ class SigMaterial:
                 for a in range(lo, hi, step):
                     b = min(hi, a + step)
                     pts = A.index_select(0, uniq[a:b].to(dev)).contiguous()
-                    g2_tab(pts, out=g2[a * E: b * E])
+                    lay.g2_table(pts, out=g2[a * E: b * E])
                     gphi = nt.pairing(bn.g1_generator_aff(dev).expand(b - a, 16).contiguous(), pts)
-                    gt_tab(gphi, out=gt[a * E: b * E])
+                    lay.gt_table(gphi, out=gt[a * E: b * E])
             if shard is not None:
                 with timers.span("rp.prove.tables4.share"):
                     for r, (a, b) in enumerate(bounds):
@@ -399,7 +427,8 @@ class SigMaterial:
         mode = self.table_mode(dev)
         if mode == 0:
             return None
-        if mode in (4, 6, 7):
+        lay = LAYOUT_OF_MODE[mode]
+        if lay.whole_set:
             g2, gt, slot = self._prover_tables4(dev, mode)
             return g2, gt, slot.index_select(0, a_idx.to(dev)), mode
         canon = self.canon.to(a_idx.device).index_select(0, a_idx)
@@ -409,9 +438,9 @@ class SigMaterial:
         missing = [int(u) for u in uniq.tolist() if int(u) not in cache["pos"]]
         if missing:
             pts = self.A.to(dev).index_select(0, torch.tensor(missing, dtype=torch.long, device=dev)).contiguous()
-            g2 = nt.g2_fb_table(pts)
+            g2 = lay.g2_table(pts)
             gphi = nt.pairing(bn.g1_generator_aff(dev).expand(len(missing), 16).contiguous(), pts)
-            gt = nt.gt_fb_table(gphi)
+            gt = lay.gt_table(gphi)
             cache["g2"] = g2 if cache["g2"] is None else torch.cat([cache["g2"], g2])
             cache["gt"] = gt if cache["gt"] is None else torch.cat([cache["gt"], gt])
             bn.publish(cache["g2"], cache["gt"])
@@ -419,7 +448,7 @@ class SigMaterial:
                 cache["pos"][m] = len(cache["idx"])
                 cache["idx"].append(m)
         slot_of_uniq = torch.tensor([cache["pos"][int(u)] for u in uniq.tolist()], dtype=torch.long, device=dev)
-        return cache["g2"], cache["gt"], slot_of_uniq.index_select(0, inv.to(dev)), 8
+        return cache["g2"], cache["gt"], slot_of_uniq.index_select(0, inv.to(dev)), mode
 
 
 _gt_cache: dict = {}
@@ -767,7 +796,7 @@ def _prove_group(u, l, vals, offs, cols, r, cv, sigmat, P_point, device, mode=0,
         g2_tabs, gphi_tabs, slot, wbits = tabs
         tidx = slot.index_select(0, inv).to(torch.int32).contiguous()
         with timers.span("rp.prove.V"):
-            V = {4: nt.g2_fb4_mul, 6: nt.g2_gls6_mul, 7: nt.g2_gls8_mul, 8: nt.g2_fb_mul}[wbits](g2_tabs, v, tidx)
+            V = LAYOUT_OF_MODE[wbits].g2_mul(g2_tabs, v, tidx)
         negs_rep = nt.fr_arith(nt.FR_NEG, s).view(n, 1, l, 8).expand(n, S, l, 8).reshape(-1, 8).contiguous()
         e = nt.fr_arith(nt.FR_MUL, negs_rep, v)
         with timers.span("rp.prove.A"):

@@ -312,11 +312,26 @@ def test_fb4_combs_match_oracle(gpu_device):
     assert torch.equal(nt.gt_fb4_pow(gt_tab, k), nt.gt_pow(e.expand(len(ks), 96).contiguous(), k))
 
 
-@pytest.mark.parametrize("bits", ["8", "7", "6", "4", "0"])
+def test_gls8_g2_table_gpu_matches_host(gpu_device):
+    """g2_gls8_mul on gfx950 vs the host path, bit for bit: the two-base table
+    and edge scalars of test_native_bn254, tiled to 70 rows (one full 64-lane
+    workgroup of g2_mul_kernel and a partial one), alternating the bases."""
+    import test_native_bn254 as nb
+
+    bases, ks = nb.gls8_g2_case()
+    ks = ks * 5
+    assert len(ks) == 70
+    A, k = bn.g2_aff_tensor(bases), bn.scalars_tensor(ks)
+    idx = torch.tensor([i % 2 for i in range(70)], dtype=torch.int32)
+    c, g = _both(lambda a, kk, ii: nt.g2_gls8_mul(nt.g2_gls8_table(a), kk, ii), A, k, idx)
+    assert torch.equal(c, g)
+
+
+@pytest.mark.parametrize("bits", ["8", "7", "4", "0"])
 def test_range_prover_layouts_gpu(gpu_device, bits, monkeypatch):
     """Every prover path on the GPU with random per-CN, per-column keys:
-    8-bit combs, the HBM-sized 4-bit combs, and the table-free path
-    (variable-base G2 + one pairing per item)."""
+    8-bit combs, GLS-2 signed 8-bit tables, the HBM-sized 4-bit combs, and the
+    table-free path (variable-base G2 + one pairing per item)."""
     from drynx_amd.crypto import elgamal as eg
     from drynx_amd.ops.encoding import CreateProofBatch
     from drynx_amd.proofs import range_proof as rp

@@ -164,21 +164,31 @@ def test_glv_weight_constants_match_oracle():
         assert r == a + b * nt.GLV_LAMBDA  # < r: no reduction, all 2^64 (a, b) distinct
 
 
-def test_gls6_tables_match_oracle():
-    """GLS-2 6-bit tables (prover mode 6): k A = k0 A + psi(k1 A) and
-    E^k = E^k0 frob(E^k1) with k = k0 + k1 * 6u^2 -- against the oracle."""
-    import random
-
-    from drynx_amd import native as nt
-    from drynx_amd.crypto import bn254 as bn
-    from drynx_amd.crypto import oracle as O
-
+def gls8_g2_case():
+    """Two random G2 bases and the scalars at the edges of the GLS-2 split
+    k = k0 + k1 lambda (lambda = 6u^2) and of its signed byte windows: an empty
+    k1 half, an empty k0 half and the carry out of the top window (0, 1, r - 1,
+    lambda, lambda - 1); digit +128, the last table entry, without a carry
+    (128); digit -127 with a carry into the next window (129); both in either
+    half; and five random scalars."""
     rng = random.Random(3)
-    A = O.g2_mul(rng.randrange(1, O.R), O.G2_GEN)
-    E = O.pairing(O.g1_mul(5, O.G1_GEN), A)
-    ks = [rng.randrange(O.R) for _ in range(5)] + [0, 1, O.R - 1, 6 * O.U * O.U, 6 * O.U * O.U - 1]
-    kt = bn.scalars_tensor(ks)
-    g2 = nt.g2_gls6_mul(nt.g2_gls6_table(bn.g2_aff_tensor([A])), kt)
-    assert bn.g2_points_from_aff(g2) == [None if k % O.R == 0 else O.g2_mul(k, A) for k in ks]
-    gt = nt.gt_gls6_pow(nt.gt_gls6_table(bn.gt_tensor([E])), kt)
-    assert bn.gt_from_tensor(gt) == [E ** k for k in ks]
+    lam = 6 * O.U * O.U
+    bases = [O.g2_mul(rng.randrange(1, O.R), O.G2_GEN) for _ in range(2)]
+    ks = [0, 1, O.R - 1, lam, lam - 1, 128, 129, 2**128 - 1 + lam, lam * 129 + 128]
+    return bases, ks + [rng.randrange(O.R) for _ in range(5)]
+
+
+def test_gls8_g2_table_matches_oracle():
+    """GLS-2 signed 8-bit G2 tables (prover mode 7): k A = k0 A + psi(k1 A)
+    against the oracle, from the first table (no tab_idx) and from two tables
+    by an alternating tab_idx."""
+    bases, ks = gls8_g2_case()
+    tab, kt = nt.g2_gls8_table(bn.g2_aff_tensor(bases)), bn.scalars_tensor(ks)
+
+    def want(k, A):
+        return None if k % O.R == 0 else O.g2_mul(k, A)
+
+    assert bn.g2_points_from_aff(nt.g2_gls8_mul(tab, kt)) == [want(k, bases[0]) for k in ks]
+    idx = [i % 2 for i in range(len(ks))]
+    got = nt.g2_gls8_mul(tab, kt, torch.tensor(idx, dtype=torch.int32))
+    assert bn.g2_points_from_aff(got) == [want(k, bases[i]) for k, i in zip(ks, idx)]

@@ -96,11 +96,20 @@ def test_device_challenge_hash_matches_sha3_512():
     assert got == exp
 
 
-@pytest.mark.parametrize("bits", ["8", "7", "6", "4", "0"])
+@pytest.mark.parametrize("bits", ["6", "5"])
+def test_prover_table_bits_outside_the_layouts_raise(setup, bits, monkeypatch):
+    """DRYNX_PROVER_TABLE_BITS takes the modes of rp.PROVER_LAYOUTS and 0;
+    anything else (6: the retired GLS-2 6-bit layout) is an error, not "auto"."""
+    monkeypatch.setenv("DRYNX_PROVER_TABLE_BITS", bits)
+    with pytest.raises(ValueError, match="0, 4, 7, 8"):
+        rp.SigMaterial(setup[3]).table_mode("cpu")
+
+
+@pytest.mark.parametrize("bits", ["8", "7", "4", "0"])
 def test_prover_table_layouts_agree(setup, bits, monkeypatch):
-    """8-bit combs, 4-bit (HBM-sized, random per-CN per-column keys) and the
-    table-free prover all produce proofs the batched and the per-equation
-    reference verifiers accept."""
+    """8-bit combs, GLS-2 signed 8-bit, 4-bit (HBM-sized, random per-CN
+    per-column keys) and the table-free prover all produce proofs the batched
+    and the per-equation reference verifiers accept."""
     S, u, l, sigs, _, P, pk = setup
     monkeypatch.setenv("DRYNX_PROVER_TABLE_BITS", bits)
     sm = rp.SigMaterial(sigs)  # fresh: the layout is chosen once per signature set

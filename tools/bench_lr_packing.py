@@ -54,11 +54,11 @@ def table_plan(args, device) -> str | None:
         return os.environ["DRYNX_PROVER_TABLE_BITS"]
     if device.type != "cuda":
         return None
-    from drynx_amd import native as nt
+    from drynx_amd.proofs.range_proof import LAYOUT_OF_MODE
 
     n_out = [lr_nbr_outputs(args.features, 2, p) for p in LAYOUTS.values()]
     points = args.cns * args.u * sum(n_out)
-    tables = points * nt.GLS8_ENTRIES * (128 + 192)
+    tables = points * LAYOUT_OF_MODE[7].bytes_per_point
     reserve = int((48 << 30) * max(1.0, args.dps * n_out[0] / HEADLINE_PROOFS))
     if tables + reserve <= torch.cuda.mem_get_info(device)[0]:
         return None
