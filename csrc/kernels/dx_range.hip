@@ -14,7 +14,7 @@
 //            The Miller product is regrouped by bilinearity (dx_rpmsm.hip) and
 //            folded by dx_fold.hip / dx_ufold_coop.hip; this file has the
 //            prod a^rho side: the segmented products and bucket weights of
-//            its multi-exponentiation (native/__init__.py multi_exp_grouped).
+//            its multi-exponentiation (native/msm.py multi_exp_grouped).
 // Item index: it = (p * S + i) * L + j.
 #include "common.h"
 #include "../bn254/gt_coop.h"

@@ -39,6 +39,8 @@ import io
 import math
 import os
 import threading
+from collections import namedtuple
+from contextlib import nullcontext
 from dataclasses import dataclass
 from typing import Callable
 
@@ -834,16 +836,12 @@ def _rand64(n, device, bits: int = 64) -> torch.Tensor:
     return mask_bits(bn.random_scalars(n, device), bits)
 
 
-def _gt_in_subgroup(g: torch.Tensor) -> bool:
-    """Host test that cyclotomic elements are in GT (order r): g^p == g^(6u^2)
-    (p = 6u^2 mod r for BN curves; Scott's membership test)."""
-    return all(_gt_in_subgroup_each(g))
-
-
 def _gt_in_subgroup_each(g: torch.Tensor) -> list:
-    """``_gt_in_subgroup`` of every row of [k, 96] -> [bool] (one host batch:
-    x^p by a Frobenius map against x^(6u^2) by two cyclotomic u-ladders; the
-    rows are products of validated cyclotomic a_ij)."""
+    """Host test that cyclotomic elements are in GT (order r): g^p == g^(6u^2)
+    (p = 6u^2 mod r for BN curves; Scott's membership test) for every row of
+    [k, 96] -> [bool] (one host batch: x^p by a Frobenius map against x^(6u^2)
+    by two cyclotomic u-ladders; the rows are products of validated cyclotomic
+    a_ij)."""
     return [bool(v) for v in nt.gt_membership(g.cpu().contiguous()).tolist()]
 
 
@@ -880,6 +878,80 @@ def validate_list(r: RangeProofList, mode: int = 0, subgroup: bool | None = None
     return ok if lazy else bool(ok)
 
 
+class Sides(namedtuple("Sides", "lhs e dl dr eq d_ok")):
+    """Both sides of K batch equations, host tensors: ``lhs`` [K, 96] against gT^``e`` (``e``
+    [K, 8]) -> ``eq``, ``dl`` against ``dr`` ([K, 24]) -> ``d_ok`` ([bool] per row)."""
+
+    @staticmethod
+    def compare(lhs, e, dl, dr, gt_tab) -> "Sides":
+        eq, d_ok = nt.gt_eq(lhs, nt.gt_fb_pow(gt_tab, e)), nt.g1_eq(dl, dr)
+        return Sides(lhs, e, dl, dr, [bool(x) for x in eq.tolist()], [bool(x) for x in d_ok.tolist()])
+
+    def rest(self, v: int, parts: "Sides", gt_tab) -> "Sides":
+        """Row ``v`` without ``parts`` (equations over disjoint subsets of row v's proofs, same
+        weights): lhs divided by their product, e, dl and dr less their sums, compared again."""
+        k, v1 = parts.lhs.shape[0], slice(v, v + 1)
+        lhs = nt.gt_mul(self.lhs[v1].contiguous(), nt.gt_inv(nt.gt_prod(parts.lhs.view(k, 1, 96), chunk=64)))
+        e = nt.fr_arith(nt.FR_SUB, self.e[v1].contiguous(), nt.fr_seg_sum(parts.e.contiguous(), torch.tensor([0, k])))
+        dl = nt.g1_add(self.dl[v1].contiguous(), nt.g1_sum(parts.dl.view(k, 1, 24)), subtract=True)
+        dr = nt.g1_add(self.dr[v1].contiguous(), nt.g1_sum(parts.dr.view(k, 1, 24)), subtract=True)
+        return Sides.compare(lhs, e, dl, dr, gt_tab)
+
+
+def _close(F, GG, e, D, dd, PB_base, gt_tab) -> Sides:
+    """The closing of K batch equations on the host, one native call each: the same for a VN's
+    whole batch and for a (VN, segment) pair.  F [K, 96]: U-side product times ML(B, R), before the
+    final exponentiation; GG [K, 96]: prod a^rho; e [K, 8]: sum rho Zv; D [K, 2, 24]: sum w c C'
+    and sum w D; dd [K, 2, 8]: sum w Zr and sum w z; PB_base: (P, B).
+      lhs = FE(F) * GG  against  gT^e;   dl = D[0] + dd[0] P + dd[1] B  against  dr = D[1]"""
+    with timers.span("rp.verify.final_exp"):
+        lhs = nt.gt_mul(nt.final_exp(F.contiguous()), GG.contiguous())
+    PB = nt.g1_mul(PB_base.repeat(F.shape[0], 1), dd.reshape(-1, 8).contiguous()).view(-1, 2, 24)
+    dl = nt.g1_sum(torch.stack([D[:, 0], PB[:, 0], PB[:, 1]]).contiguous())
+    return Sides.compare(lhs, e.contiguous(), dl, D[:, 1].contiguous(), gt_tab)
+
+
+class FirstPass(namedtuple("FirstPass", "rho ab gam w A2 Cp z useg u_seg m_first wc PB_base gt_tab G tot GGgam r_ok")):
+    """What the first pass hands to the attribution of its failing VNs: the G VNs' weights (VN-major
+    rows: ``rho`` [G m, 8], its GLV halves ``ab``, ``gam``, ``w`` [G n, 8]), the weight-free inputs,
+    per (VN, segment) the U-side products ``useg`` (host) and G2 flags ``u_seg``, and per VN the
+    first pass's results: ``tot`` (``_close`` of its whole batch), ``GGgam`` (prod a^gamma, host),
+    ``m_first`` (GGgam in GT), ``r_ok`` (R in G2)."""
+
+    def select(self, v: int, T: list, segs: list) -> "FirstPass":
+        """VN ``v`` alone (G = 1) over the proofs and items of the segments ``T``."""
+        G, dev = self.G, self.rho.device
+        n, m = self.w.shape[0] // G, self.rho.shape[0] // G
+        poff = np.cumsum([0] + list(segs))
+        pidx = torch.cat([torch.arange(int(poff[s]), int(poff[s + 1])) for s in T])
+        iidx = (pidx.view(-1, 1) * (m // n) + torch.arange(m // n).view(1, -1)).reshape(-1)
+        pidx, iidx = bn.h2d(pidx, dev), bn.h2d(iidx, dev)
+        sel = lambda t, w, idx: t.view(G, -1, w)[v].index_select(0, idx).contiguous()  # noqa: E731
+        Tt = bn.h2d(torch.tensor(T), self.u_seg.device)
+        return self._replace(
+            A2=self.A2.index_select(0, torch.cat([iidx, iidx + m])), rho=sel(self.rho, 8, iidx),
+            ab=sel(self.ab, 2, iidx), gam=sel(self.gam, 8, iidx), w=sel(self.w, 8, pidx),
+            Cp=self.Cp.index_select(0, pidx), z=self.z.index_select(0, pidx), useg=self.useg[v: v + 1, T],
+            u_seg=self.u_seg[v: v + 1].index_select(1, Tt), G=1, m_first=[self.m_first[v]],
+            tot=Sides(*(f[v: v + 1] for f in self.tot)), GGgam=self.GGgam[v: v + 1], r_ok=[self.r_ok[v]])
+
+
+def _c_prime(r: RangeProofList, device, tabB=None) -> torch.Tensor:
+    """C' = C + offset*B per proof (C itself when no proof carries an offset)."""
+    if not any(r.offset):
+        return r.commit.C
+    tabB = bn.base_table(device) if tabB is None else tabB
+    return nt.g1_add(r.commit.C, nt.g1_fb_mul_i64(tabB, bn.h2d(torch.tensor(r.offset, dtype=torch.int64), device)))
+
+
+def _dcheck_inputs(Cp, D, w, challenge, G: int):
+    """D-check MSM of G weight sets ``w`` [G n, 8]: rows (v, which, p), which = 0: (w c) C', 1: w D."""
+    dpts = torch.cat([Cp.contiguous(), D.contiguous()]).repeat(G, 1)
+    wc = nt.fr_arith(nt.FR_MUL, w, challenge)
+    dsc = torch.stack([wc.view(G, -1, 8), w.view(G, -1, 8)], 1).reshape(-1, 8).contiguous()
+    return dpts, dsc
+
+
 def verify_range_proof_list(rpl: RangeProofList, sigmat: SigMaterial, P_point, threshold: float = 1.0,
                             device=None, mode: int = 0, coins=None) -> bool:
     """RangeProofListVerification: verifies the first ceil(threshold * n)
@@ -892,7 +964,7 @@ def verify_range_proof_list(rpl: RangeProofList, sigmat: SigMaterial, P_point, t
     k = int(math.ceil(threshold * len(rpl)))
     if k == 0:
         return True
-    r = rpl if k == len(rpl) else _slice(rpl, k)
+    r = rpl if k == len(rpl) else rpl_range(rpl, 0, k)
     return verify_range_proof_list_multi(r, sigmat, P_point, 1, device, mode, coins=[coins])[0]
 
 
@@ -911,21 +983,21 @@ def verify_range_proof_list_multi(r: RangeProofList, sigmat: SigMaterial, P_poin
       sum w (c C') + (sum w Zr) P + (sum w z) B == sum w D       (one MSM)
     plus GT membership of the a_it: each VN's own independent 40-bit
     combination gamma_v.  What does not depend on the weights -- decoding
-    checks, the strict-mode
-    challenge and G2 checks, Zphi*B, c*y_i and their differences -- is
-    computed once for the co-hosted VNs.  On a GPU the VNs' Miller folds are
-    queued back to back (no host round trip between them) while the
-    bucket-method MSM / multi-exponentiations run on a side stream; the
-    closing single-element work (final exponentiations, Horner steps) runs
-    on the host, where one core beats one GPU lane.  -> [bool] per VN.
+    checks, the strict-mode challenge and G2 checks, Zphi*B, c*y_i and their
+    differences -- is computed once for the co-hosted VNs.  On a GPU the VNs'
+    Miller folds are queued back to back (no host round trip between them)
+    while the bucket-method MSM / multi-exponentiations run on a side stream;
+    the closing single-element work (final exponentiations, Horner steps)
+    runs on the host, where one core beats one GPU lane, for all VNs in one
+    batch (``_close``).  -> [bool] per VN.
 
     ``segs`` (proof counts summing to len(r): the batch's per-request
     slices) asks for attribution: -> per VN a [bool] per segment, None when
-    a failed batch cannot be attributed, or a
-    ``RangeInvalid`` (per segment: decodes) when some proofs do not decode.  The U side is then laid out per segment
-    (each segment's U_q start whole accumulation workgroups, so each has its
-    own Miller partial products -- no extra pairing work), and only a VN
-    whose batch FAILS pays a second, segment-grouped pass over the cheap
+    a failed batch cannot be attributed, or a ``RangeInvalid`` (per segment:
+    decodes) when some proofs do not decode.  The U side is then laid out per
+    segment (each segment's U_q start whole accumulation workgroups, so each
+    has its own Miller partial products -- no extra pairing work), and only a
+    VN whose batch FAILS pays a second, segment-grouped pass over the cheap
     sides (R MSM, multi-exponentiation, D-check, exponent sums) with the same
     weights: blame costs ~one VN's MSMs, not a bisection of re-verifications.
 
@@ -968,11 +1040,7 @@ def verify_range_proof_list_multi(r: RangeProofList, sigmat: SigMaterial, P_poin
                 ev_valid = torch.cuda.Event()
                 ev_valid.record(vstream)                      # the weight mask waits for this, not for c C'
                 if ddirect:  # c C' per proof, weight-free (undecodable rows are masked out later)
-                    cC = nt.g1_mul(r.commit.C.contiguous() if not any(r.offset) else
-                                   nt.g1_add(r.commit.C, nt.g1_fb_mul_i64(
-                                       bn.base_table(device), bn.h2d(torch.tensor(r.offset, dtype=torch.int64),
-                                                                     device))),
-                                   r.challenge.contiguous())
+                    cC = nt.g1_mul(_c_prime(r, device).contiguous(), r.challenge.contiguous())
                     ev_cC = torch.cuda.Event()
                     ev_cC.record(vstream)
         else:
@@ -1001,49 +1069,46 @@ def verify_range_proof_list_multi(r: RangeProofList, sigmat: SigMaterial, P_poin
     def _cat_draw(fn):
         return torch.cat([fn(c) for c in cl]) if G > 1 else fn(cl[0])
 
-    _sw = timers.span("rp.verify.weights")
-    _sw.__enter__()
-    # D-equation weights, GLV-shaped like rho (a + b lambda, 32-bit halves:
-    # the same 2^-64 soundness as uniform 64-bit weights), so the D-check can
-    # run as 32-doubling GLV ladders with no bucket plan
-    wpairs = [c.glv(n, device) if c is not None else nt.glv_weights(n, device) for c in cl]
-    wab_all = torch.cat([p_[0] for p_ in wpairs]) if G > 1 else wpairs[0][0]
-    w_all = torch.cat([p_[1] for p_ in wpairs]) if G > 1 else wpairs[0][1]
-    # pairing-equation weights: rho = a + b lambda (GLV, a and b 32-bit: 2^64
-    # distinct residues, so the same 2^-64 soundness as uniform 64-bit weights;
-    # csrc/kernels/dx_glv.hip)
-    pairs = [c.glv(m, device) if c is not None else nt.glv_weights(m, device) for c in cl]
-    ab_all = torch.cat([p_[0] for p_ in pairs]) if G > 1 else pairs[0][0]
-    rho_all = torch.cat([p_[1] for p_ in pairs]) if G > 1 else pairs[0][1]
-    # GT-membership combinations: one independent 40-bit gamma set PER VN
-    gb = _gamma_bits()
-    gam_all = _cat_draw(lambda c: c.bits(m, device, gb) if c is not None else _rand64(m, device, gb))
-    # attribution: undecodable proofs (and, mode >= 1, wrong challenges) get
-    # ZERO weights -- every weighted sum then runs over the decodable proofs
-    # only (their U_q and -c y_i become infinity, as the fold's padding), so
-    # one bad payload costs no second pass: the batch verdict IS the verdict
-    # of the decodable segments
-    masked = segs is not None
-    vm = None
-    if masked:
-        if ev_valid is not None:
-            torch.cuda.current_stream(device).wait_event(ev_valid)
-        vm = (valid if chk is None else valid & chk).to(torch.int32)
-        mi = vm.repeat_interleave(S * l).view(1, m, 1)
-        w_all = (w_all.view(G, n, 8) * vm.view(1, n, 1)).view(G * n, 8)
-        wab_all = (wab_all.view(G, n, 2) * vm.view(1, n, 1)).view(G * n, 2)
-        ab_all = (ab_all.view(G, m, 2) * mi).view(G * m, 2)
-        rho_all = (rho_all.view(G, m, 8) * mi).view(G * m, 8)
-        gam_all = (gam_all.view(G, m, 8) * mi).view(G * m, 8)
-    _sw.__exit__(None, None, None)
-    vns = [{"rho": rho_all[v * m:(v + 1) * m], "ab": ab_all[v * m:(v + 1) * m]} for v in range(G)]
+    with timers.span("rp.verify.weights"):
+        # D-equation weights, GLV-shaped like rho (a + b lambda, 32-bit halves:
+        # the same 2^-64 soundness as uniform 64-bit weights), so the D-check can
+        # run as 32-doubling GLV ladders with no bucket plan
+        wpairs = [c.glv(n, device) if c is not None else nt.glv_weights(n, device) for c in cl]
+        wab_all = torch.cat([p_[0] for p_ in wpairs]) if G > 1 else wpairs[0][0]
+        w_all = torch.cat([p_[1] for p_ in wpairs]) if G > 1 else wpairs[0][1]
+        # pairing-equation weights: rho = a + b lambda (GLV, a and b 32-bit: 2^64
+        # distinct residues, so the same 2^-64 soundness as uniform 64-bit weights;
+        # csrc/kernels/dx_glv.hip)
+        pairs = [c.glv(m, device) if c is not None else nt.glv_weights(m, device) for c in cl]
+        ab_all = torch.cat([p_[0] for p_ in pairs]) if G > 1 else pairs[0][0]
+        rho_all = torch.cat([p_[1] for p_ in pairs]) if G > 1 else pairs[0][1]
+        # GT-membership combinations: one independent 40-bit gamma set PER VN
+        gb = _gamma_bits()
+        gam_all = _cat_draw(lambda c: c.bits(m, device, gb) if c is not None else _rand64(m, device, gb))
+        # attribution: undecodable proofs (and, mode >= 1, wrong challenges) get
+        # ZERO weights -- every weighted sum then runs over the decodable proofs
+        # only (their U_q and -c y_i become infinity, as the fold's padding), so
+        # one bad payload costs no second pass: the batch verdict IS the verdict
+        # of the decodable segments
+        masked = segs is not None
+        vm = None
+        if masked:
+            if ev_valid is not None:
+                torch.cuda.current_stream(device).wait_event(ev_valid)
+            vm = (valid if chk is None else valid & chk).to(torch.int32)
+            mi = vm.repeat_interleave(S * l).view(1, m, 1)
+            w_all = (w_all.view(G, n, 8) * vm.view(1, n, 1)).view(G * n, 8)
+            wab_all = (wab_all.view(G, n, 2) * vm.view(1, n, 1)).view(G * n, 2)
+            ab_all = (ab_all.view(G, m, 2) * mi).view(G * m, 2)
+            rho_all = (rho_all.view(G, m, 8) * mi).view(G * m, 8)
+            gam_all = (gam_all.view(G, m, 8) * mi).view(G * m, 8)
     timers.count("rp.verify.items", G * m)
     me_groups = ((2 * m, 32),) * G + ((m, gb),) * G
     # windows by cost (nt.me_window): 16 bits for a 1-GPU inbox, 11 for a pool
     # slice; the host keeps bytes (fewer buckets for its serial products)
     wc_ = nt.me_window(me_groups) if device.type == "cuda" else (5, 8)
     aux = _aux_stream(device) if device.type == "cuda" else None
-    meta = (G, m, S, l, gb, tuple(wc_), _r_window(m, G))
+    meta = BatchShape(G, m, S, l, gb, tuple(wc_), _r_window(m, G))
     ev_u = ev_r = None
     if aux is not None:
         # the R MSM needs only V, Zphi and the weights: queued on the aux stream now
@@ -1058,8 +1123,6 @@ def verify_range_proof_list_multi(r: RangeProofList, sigmat: SigMaterial, P_poin
     # by _msm_queue after the U combinations, on the U stream), and C' and
     # sum_j Zphi_j u^j for the D-check and the exponent sums (on the aux
     # stream, before the multi-exponentiation: nothing there waits for the U side)
-    inp = {}
-
     def _inputs():
         with timers.span("rp.verify.inputs"):
             cols_t = bn.h2d(torch.tensor(r.cols, dtype=torch.long), device)
@@ -1073,14 +1136,7 @@ def verify_range_proof_list_multi(r: RangeProofList, sigmat: SigMaterial, P_poin
             if vm is not None:
                 Y = Y.clone()
                 Y[:, 16:] *= vm.repeat_interleave(S).view(-1, 1)                # Z = 0: -c y_i at infinity
-        inp["Y"] = Y
         return Y
-
-    def _zcp():
-        Cp = r.commit.C                                                        # C' = C + offset*B
-        if any(r.offset):
-            Cp = nt.g1_add(Cp, nt.g1_fb_mul_i64(tabB, bn.h2d(torch.tensor(r.offset, dtype=torch.int64), device)))
-        return Cp, nt.fr_dot_rows(r.zphi, _powers(u, l, device), n, b_periodic=True)   # sum_j Zphi_j u^j
 
     # GPU: the U side on this stream (its chain of Miller-loop kernels is the
     # critical path of a small batch), the R MSM (above), the
@@ -1098,18 +1154,14 @@ def verify_range_proof_list_multi(r: RangeProofList, sigmat: SigMaterial, P_poin
     if aux is not None:
         with timers.span("rp.verify.msm_queue"):
             msq = _msm_queue(_inputs, r.V, ab_all, G, n, S, l, vstream, segs, table, ygroup=yg)
-            for v, uok in zip(vns, msq["u_ok"]):
-                v["u_ok"] = uok
         ev_u = torch.cuda.Event()                                       # the U side's fold is queued
         ev_u.record(torch.cuda.current_stream(device))
-    elif yg is None:
-        _inputs()
-    with timers.span("rp.verify.passes"), (torch.cuda.stream(aux) if aux is not None else _nullctx()):
-        Cp, z = _zcp()
+    Y0 = _inputs() if aux is None and yg is None else _inputs
+    with timers.span("rp.verify.passes"), (torch.cuda.stream(aux) if aux is not None else nullcontext()):
+        Cp = _c_prime(r, device, tabB)
+        z = nt.fr_dot_rows(r.zphi, _powers(u, l, device), n, b_periodic=True)           # sum_j Zphi_j u^j
         if not ddirect:
-            dpts = torch.cat([Cp.contiguous(), r.D.contiguous()]).repeat(G, 1)
-            wc = nt.fr_arith(nt.FR_MUL, w_all, r.challenge)
-            dsc = torch.stack([wc.view(G, n, 8), w_all.view(G, n, 8)], 1).reshape(-1, 8).contiguous()
+            dpts, dsc = _dcheck_inputs(Cp, r.D, w_all, r.challenge, G)
         if aux is None:
             S_R, hR = _pass_r(r.V, r.zphi, rho_all, meta)
         A2, mexp, e_all, dfull = _pass_me(r.A, ab_all, gam_all, rho_all, r.zv, w_all, r.zr, z, meta)
@@ -1126,9 +1178,7 @@ def verify_range_proof_list_multi(r: RangeProofList, sigmat: SigMaterial, P_poin
             else:
                 dcheck = nt.g1_msm_device(dpts, dsc, n, ((n, 254),) * (2 * G))     # group = row // n
     if aux is None:  # host: the U side after the passes
-        msq = _msm_queue(inp.get("Y", _inputs), r.V, ab_all, G, n, S, l, None, segs, ygroup=yg)
-        for v, uok in zip(vns, msq["u_ok"]):
-            v["u_ok"] = uok
+        msq = _msm_queue(Y0, r.V, ab_all, G, n, S, l, None, segs, ygroup=yg)
     useg = fR = None
     with timers.span("rp.verify.multiexp"):
         if aux is not None:
@@ -1151,22 +1201,15 @@ def verify_range_proof_list_multi(r: RangeProofList, sigmat: SigMaterial, P_poin
     with timers.span("rp.verify.fold_wait"):
         if useg is None:
             useg = _seg_products(msq)                                  # [G, nseg, 96] host
-        for k_, v in enumerate(vns):
-            v["F"] = nt.gt_prod(useg[k_].view(-1, 1, 96), chunk=64).view(1, 96)
         if fR is None:
             fR, rok = _msm_r_miller(hR, S_R)
-        for v, f, ok in zip(vns, fR, rok):
-            v["F"], v["r_ok"] = nt.gt_mul(v["F"], f.view(1, 96)), ok
-    for k, v in enumerate(vns):
-        v.update(G=GG[k: k + 1], dfull=dfull[k], e=e_all[k: k + 1], dcheck=D_all[2 * k: 2 * k + 2])
+        F = nt.gt_mul(nt.gt_prod(useg.transpose(0, 1), chunk=64), fR)   # [G, 96]: U-side product * ML(B, R)
     if vstream is not None:
         vstream.synchronize()
     if chk is not None:
         valid = valid & chk
-    if vstream is not None:
-        if not bool(valid.all()) and segs is None:
-            return _invalid(valid, segs, n_vn)
-    out = []
+    if vstream is not None and not bool(valid.all()) and segs is None:
+        return _invalid(valid, segs, n_vn)
     # prime-order part of the a_ij: each VN's own independent 40-bit
     # combination in GT (the smallest prime factor of the cyclotomic cofactor
     # is ~2^38.8: a non-GT component survives the batch equation AND this test
@@ -1174,27 +1217,19 @@ def verify_range_proof_list_multi(r: RangeProofList, sigmat: SigMaterial, P_poin
     m_oks = _gt_in_subgroup_each(GG[G: 2 * G])
     _, gt_tab = gt_generator_table("cpu")
     PB_base = bn.g1_jac_tensor([P_point, O.G1_GEN], "cpu")
-    with timers.span("rp.verify.final_exp"):
-        # every VN's final exponentiation in one host batch (one core each)
-        fe = nt.final_exp(torch.cat([v["F"].cpu().view(1, 96) for v in vns]).contiguous())
-    for k_, v in enumerate(vns):
-        with timers.span("rp.verify.finish"):
-            G0 = v["dcheck"]
-            PB = nt.g1_mul(PB_base, v["dfull"])
-            v["dl"] = nt.g1_sum(torch.stack([G0[0:1], PB[0:1], PB[1:2]]))
-            d_ok = bool(nt.g1_eq(v["dl"], G0[1:2])[0])
-            v["lhs"] = lhs = nt.gt_mul(fe[k_: k_ + 1].contiguous(), v["G"].cpu())
-            eq_ok = bool(nt.gt_eq(lhs, nt.gt_fb_pow(gt_tab, v["e"].cpu())).all())
-        # regrouped ("msm") check: the U_q and R of this VN must lie in G2 --
-        # then their torsion parts (V_it off G2 by a cofactor component) cancel
-        # and the checked equation is the one of the proof's G2 projection,
-        # where the pairing is bilinear and the regrouping exact
-        g2_ok = bool(v.get("u_ok", True)) and bool(v.get("r_ok", True))
-        out.append(d_ok and m_oks[len(out)] and eq_ok and g2_ok)
-        if not out[-1]:
-            log.warning(f"range batch of {n} proofs failed for verifier {len(out) - 1}: D-check {d_ok}, "
-                        f"GT membership {m_oks[len(out) - 1]}, pairing equation {eq_ok}, "
-                        f"U in G2 {bool(v.get('u_ok', True))}, R in G2 {bool(v.get('r_ok', True))}")
+    with timers.span("rp.verify.finish"):
+        tot = _close(F, GG[:G].cpu(), e_all, D_all.view(G, 2, 24), dfull, PB_base, gt_tab)
+    # regrouped ("msm") check: the U_q and R of a VN must lie in G2 -- then
+    # their torsion parts (V_it off G2 by a cofactor component) cancel and the
+    # checked equation is the one of the proof's G2 projection, where the
+    # pairing is bilinear and the regrouping exact
+    u_ok = [bool(ok) for ok in msq.u_ok]
+    out = [tot.d_ok[v] and m_oks[v] and tot.eq[v] and u_ok[v] and rok[v] for v in range(G)]
+    for v in range(G):
+        if not out[v]:
+            log.warning(f"range batch of {n} proofs failed for verifier {v}: D-check {tot.d_ok[v]}, "
+                        f"GT membership {m_oks[v]}, pairing equation {tot.eq[v]}, "
+                        f"U in G2 {u_ok[v]}, R in G2 {rok[v]}")
     if segs is None:
         return out
     # attribution: a passing batch clears every segment; a failing one gets
@@ -1206,27 +1241,26 @@ def verify_range_proof_list_multi(r: RangeProofList, sigmat: SigMaterial, P_poin
     redo = [k_ for k_ in range(G) if not out[k_] or (seg_valid is not None and not masked)]
     res = [([True] * nseg if seg_valid is None else list(seg_valid)) if ok else None for ok in out]
     if redo:
-        if "items" in msq:  # key-grouped first pass: the per-segment U-side products only now
+        if msq.items is not None:  # key-grouped first pass: the per-segment U-side products only now
             with timers.span("rp.verify.useg_items"):
                 useg = _useg_items(msq)
         with timers.span("rp.verify.segments"):
             if A2 is None:  # torus first pass: the segment passes' Fp12 rows only now
                 A2 = _stack_frob8(r.A)
-            x = dict(A2=A2, rho=rho_all, ab=ab_all, gam=gam_all, w=w_all, Cp=Cp, z=z, useg=useg, u_seg=msq["u_seg"],
-                     # the segment pass keeps host-planned 11-bit windows (its groups are
-                     # (VN, segment) pairs: 16-bit windows would mean millions of buckets)
-                     PB_base=PB_base, gt_tab=gt_tab, wc=(4, 11) if device.type == "cuda" else wc_, G=G,
-                     # undecodable proofs in an UNMASKED batch: the first pass's GT
-                     # combination included a_ij not known to be cyclotomic, so it
-                     # bounds nothing -- every segment then gets its own combination
-                     m_first=m_oks if seg_valid is None or masked else [False] * G,
-                     tot=dict(lhs=[v.get("lhs") for v in vns], e=e_all, GGgam=GG[G: 2 * G],
-                              dl=[v.get("dl") for v in vns], dr=[v["dcheck"][1:2] for v in vns],
-                              r_ok=[bool(v.get("r_ok", True)) for v in vns]))
+            x = FirstPass(
+                rho=rho_all, ab=ab_all, gam=gam_all, w=w_all, A2=A2, Cp=Cp, z=z, useg=useg, u_seg=msq.u_seg,
+                # undecodable proofs in an UNMASKED batch: the first pass's GT
+                # combination included a_ij not known to be cyclotomic, so it
+                # bounds nothing -- every segment then gets its own combination
+                m_first=m_oks if seg_valid is None or masked else [False] * G,
+                # the segment pass keeps host-planned 11-bit windows (its groups are
+                # (VN, segment) pairs: 16-bit windows would mean millions of buckets)
+                wc=(4, 11) if device.type == "cuda" else wc_, PB_base=PB_base, gt_tab=gt_tab, G=G,
+                tot=tot, GGgam=GG[G: 2 * G].cpu(), r_ok=rok)
             if masked or seg_valid is None:
                 per = _attribute_hinted(r, segs, redo, x)
             else:
-                per = _segment_pass(r, segs, redo, x)
+                per = _segment_pass(r, segs, redo, x).per
         for k_ in redo:
             if seg_valid is not None:
                 per_k = [a and b for a, b in zip(per[k_], seg_valid)]
@@ -1275,16 +1309,11 @@ def run_idle_tasks():
         tasks.pop(0).run()
 
 
-class _nullctx:
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        return False
-
-
 _SHAPE_INDEX: dict = {}
 _SHAPE_INDEX_MAX = 16
+# Shape of a first pass: G VNs, m = n S l items; gb: bits of the GT-membership
+# weights, wc: (W, c) of the multi-exponentiation, cR: window of the R MSM
+BatchShape = namedtuple("BatchShape", "G m S l gb wc cR")
 
 
 def _shape_index(key, device, fn, n: int) -> torch.Tensor:
@@ -1308,15 +1337,15 @@ def _shape_index(key, device, fn, n: int) -> torch.Tensor:
     return t
 
 
-def _pass_r(V, zphi, rho, meta):
+def _pass_r(V, zphi, rho, meta: BatchShape):
     """R = sum_it (rho_it Zphi_(p, j)) V_it per VN: the G2 Pippenger MSM with a
     device plan, queued on the current stream (no host sync) -> (S_R, hR)."""
-    G, m, S, l, gb, wc, cR = meta
+    G, m, S, l = meta.G, meta.m, meta.S, meta.l
     zi = _shape_index(("zphi", m, S, l), V.device,
                       lambda it: (it // (S * l)) * l + it % l, m)        # item -> its Zphi row
     s_r = nt.fr_arith(nt.FR_MUL, rho, zphi.index_select(0, zi).contiguous())
     with timers.span("rp.run.R"):
-        return nt.g2_msm_device(V, s_r, m, ((m, 254),) * G, c=cR)
+        return nt.g2_msm_device(V, s_r, m, ((m, 254),) * G, c=meta.cR)
 
 
 _ME_TORUS_DEFAULT = "1"  # measured: profiles/me_torus/README.md
@@ -1340,14 +1369,14 @@ def _stack_frob8(A: torch.Tensor) -> torch.Tensor:
     return A2
 
 
-def _pass_me(A, ab, gam, rho, zv, w, zr, z, meta):
+def _pass_me(A, ab, gam, rho, zv, w, zr, z, meta: BatchShape):
     """The GT multi-exponentiation over (A, frob^8 A) with the GLV halves of
     rho (groups 0..G-1) and each VN's 40-bit membership combination (G..2G-1),
     and the Fr exponent sums, on the current stream -> (A2, mexp, e_all, dfull).
     On the torus path (``_me_torus``) the source is the stacked torus images
     instead and A2 is None: only a failing batch's segment passes need it
     (``_stack_frob8``)."""
-    G, m, S, l, gb, wc, cR = meta
+    G, m, gb, wc = meta.G, meta.m, meta.gb, meta.wc
     dev = A.device
     torus = _me_torus()
     with timers.span("rp.frob8"):
@@ -1393,9 +1422,10 @@ def _r_window(m: int, G: int) -> int:
 _YGROUP_MIN_MULT = 3
 _KEY_GROUPS: dict = {}
 _KEY_GROUPS_MAX = 8
+KeyGroups = namedtuple("KeyGroups", "idx start len keys ng")
 
 
-def _key_groups(cols, S: int, n_cols: int, device) -> dict:
+def _key_groups(cols, S: int, n_cols: int, device) -> KeyGroups:
     """The U rows q = p*S + i of a proof list grouped by their G1 key
     ``y_idx = i * n_cols + cols[p]``: "idx" (int32 [n*S], the q's sorted by
     group), "start" / "len" per group, "keys" (the groups' y_idx) and "ng".
@@ -1423,28 +1453,34 @@ def _key_groups(cols, S: int, n_cols: int, device) -> dict:
               _h2d((np.cumsum(ln) - ln).astype(np.int64), dev), _h2d(ln.astype(np.int32), dev),
               _h2d(keys.astype(np.int64), dev)]
         bn.publish(ts)
-        kg = _KEY_GROUPS[k] = dict(idx=ts[0], start=ts[1], len=ts[2], keys=ts[3], ng=len(keys))
+        kg = _KEY_GROUPS[k] = KeyGroups(idx=ts[0], start=ts[1], len=ts[2], keys=ts[3], ng=len(keys))
     if dev.type == "cuda":
-        for t in (kg["idx"], kg["start"], kg["len"], kg["keys"]):
+        for t in (kg.idx, kg.start, kg.len, kg.keys):
             t.record_stream(torch.cuda.current_stream(dev))  # a later drop waits for this reader
     return kg
 
 
+# ``_msm_queue``: "u_seg" [G, n_segments] exact G2 membership of every segment's U's, "u_ok" the
+# same per VN (on a GPU both on the validation stream), "fold" the Miller partial products, "items"
+# (None unless key-grouped) what ``_useg_items`` needs: Y, the U rows [G nq, 32], the segments' offsets
+UQueue = namedtuple("UQueue", "G u_seg u_ok fold items")
+UItems = namedtuple("UItems", "Y Uall nq qoff")
+
+
 def _msm_queue(Y, V, ab_all, G: int, n: int, S: int, L: int, vstream=None, segs: list | None = None,
-               table=None, ygroup: dict | None = None) -> dict:
+               table=None, ygroup: dict | None = None) -> UQueue:
     """Verifier mode "msm", the U side (no host sync; csrc/kernels/dx_rpmsm.hip):
     the pairing side of G verifiers' batches regrouped by bilinearity,
         prod_it ML(rho_it (Zphi_pj B - Y_pi), V_it)
           ~ ML(B, R_v) * prod_q ML(-Y_q, U_vq)         (equal after the final exp)
     with U_vq = sum_j rho_(q,j) V_(q,j) (q = p*S + i; a joint 2-bit-window
     ladder over the 15-entry per-V table shared by the VNs) and R_v the
-    Pippenger G2 MSM of ``_msm_plan`` (queued separately: ``nt.g2_msm_run``,
+    Pippenger G2 MSM of ``_pass_r`` (queued separately: ``nt.g2_msm_device``,
     finished by ``_msm_r_miller``).  GPU: the U's of all VNs form one list
     (VN-major; with ``segs``, each segment's U's start a whole accumulation
     workgroup) that the normalised fold kernels pair with uv(-Y_q) -> per-
-    workgroup partial products ("fb"), reduced per (VN, segment) by
+    workgroup partial products (``Fold``), reduced per (VN, segment) by
     ``_seg_products``; host: per-item Miller loops over the same pairs.
-    "u_seg": [G, n_segments] exact G2 membership of every segment's U's.
     ``Y`` may be a callable returning it (issued after the U combinations).
 
     ``ygroup`` (``_key_groups`` of the proofs' columns as "groups", their
@@ -1453,9 +1489,9 @@ def _msm_queue(Y, V, ab_all, G: int, n: int, S: int, L: int, vstream=None, segs:
         prod_(q in k) ML(-c_p y_k, U_vq) ~ ML(-y_k, sum_(q in k) c_p U_vq):
     one Miller loop per (VN, key) over the key-group combinations
     (``nt.rp_u_group``) and no c_p y products.  Every U_vq is still computed
-    and tested for G2 membership ("u_seg" as above); the queue then returns
-    the per-VN product only (sb = [0]) and keeps what ``_useg_items`` needs
-    for the per-segment products of a failing batch ("items")."""
+    and tested for G2 membership; the queue's fold then holds the per-VN
+    product only (sb = [0]) and ``items`` keeps what ``_useg_items`` needs
+    for the per-segment products of a failing batch."""
     dev = V.device
     nq = n * S
     qoff = np.cumsum([0] + [c * S for c in segs]) if segs else np.array([0, nq])
@@ -1463,11 +1499,10 @@ def _msm_queue(Y, V, ab_all, G: int, n: int, S: int, L: int, vstream=None, segs:
     if table is None:
         with timers.span("rp.u.joint_table"):
             table = nt.g2_joint_table(V)
-    out = {"G": G}
-    lay = pos = None
+    lay = pos = items = None
     if dev.type == "cuda" and ygroup is None:
         lay = _fold_layout(G, nq, cq, dev)
-        pad, pos = lay["pad"], lay["pos"]
+        pad, pos = lay.pad, lay.pos
         Uall = torch.zeros((G * pad, 32), dtype=torch.int32, device=dev)
     else:
         pad = nq
@@ -1485,43 +1520,49 @@ def _msm_queue(Y, V, ab_all, G: int, n: int, S: int, L: int, vstream=None, segs:
             # finish); the caller synchronises `vs` before looking at the verdicts
             flags = nt.g2_subgroup(Uall)
             fl = (flags.view(G, pad)[:, :nq] if pos is None else flags.index_select(0, pos).view(G, nq)).bool()
-            out["u_seg"] = _seg_all(fl, cq, dev)
-            out["u_ok"] = list(out["u_seg"].all(dim=1).unbind(0))
+            u_seg = _seg_all(fl, cq, dev)
+            u_ok = list(u_seg.all(dim=1).unbind(0))
         Uall.record_stream(vs)
         if pos is not None:
             pos.record_stream(vs)
     else:
-        out["u_seg"] = _seg_all(nt.g2_subgroup(Uall).view(G, nq).bool(), cq, dev)
-        out["u_ok"] = [bool(x) for x in out["u_seg"].all(dim=1).tolist()]
+        u_seg = _seg_all(nt.g2_subgroup(Uall).view(G, nq).bool(), cq, dev)
+        u_ok = [bool(x) for x in u_seg.all(dim=1).tolist()]
     if ygroup is not None:
         kg = ygroup["groups"]
-        ng = kg["ng"]
+        ng = kg.ng
         with timers.span("rp.u.group"):
             split = nt.glv_split(ygroup["challenge"].contiguous())       # per proof: k1, |k2|, sign
             sgn = split[:, 8].repeat_interleave(S).repeat(G).contiguous()
             tU = nt.g2_joint_table(Uall, sgn)                            # over (U, +-[lambda] U)
-            Yk = ygroup["y_jac"].index_select(0, kg["keys"]).contiguous()
+            Yk = ygroup["y_jac"].index_select(0, kg.keys).contiguous()
             if dev.type == "cuda":
                 lay = _fold_layout(G, ng, np.array([ng]), dev)
-                Ug = torch.zeros((G * lay["pad"], 32), dtype=torch.int32, device=dev)
+                Ug = torch.zeros((G * lay.pad, 32), dtype=torch.int32, device=dev)
             else:
                 Ug = torch.zeros((G * ng, 32), dtype=torch.int32, device=dev)
-            nt.rp_u_group(tU, split, kg["idx"], kg["start"], kg["len"], G, nq, S, Ug, Ug.shape[0] // G)
+            nt.rp_u_group(tU, split, kg.idx, kg.start, kg.len, G, nq, S, Ug, Ug.shape[0] // G)
         if dev.type == "cuda":
-            _fold_items(lay, Ug, Yk, G, ng, out)
+            fold = _fold_items(lay, Ug, Yk, G, ng)
         else:
-            _fold_items_host(Ug, Yk, G, ng, np.array([0, ng]), out)
-        out["items"] = dict(Y=Y, Uall=Uall, nq=nq, qoff=qoff)
+            fold = _fold_items_host(Ug, Yk, G, ng, np.array([0, ng]))
+        items = UItems(Y, Uall, nq, qoff)
     elif dev.type == "cuda":
-        _fold_items(lay, Uall, Y, G, nq, out)
+        fold = _fold_items(lay, Uall, Y, G, nq)
     else:
-        _fold_items_host(Uall, Y, G, nq, qoff, out)
-    return out
+        fold = _fold_items_host(Uall, Y, G, nq, qoff)
+    return UQueue(G, u_seg, u_ok, fold, items)
 
 
-def _fold_layout(G: int, nq: int, cq, dev) -> dict:
+FoldLayout = namedtuple("FoldLayout", "K rows pad period coop pos sb nb")
+# Miller partial products "fb" [blocks, 96]: "blk" blocks per VN; per segment
+# its first block "sb" and block count "nb" within a VN (``_seg_products``)
+Fold = namedtuple("Fold", "fb blk sb nb")
+
+
+def _fold_layout(G: int, nq: int, cq, dev) -> FoldLayout:
     """Rows of the GPU fold for G verifiers' nq pairs in the consecutive
-    segments ``cq``: items per lane K, the per-VN row count "pad" (one
+    segments ``cq``: items per lane "K", the per-VN row count "pad" (one
     segment: room for the (B, R) row; several: each starts whole
     accumulation workgroups, "pos" = the row of (v, q)), the padded "period"
     and the partial-product blocks per segment ("sb", "nb")."""
@@ -1552,16 +1593,16 @@ def _fold_layout(G: int, nq: int, cq, dev) -> dict:
     # one-lane accumulation over normalised lines and (x/y, 1/y) points
     # (the three-lane fold at the 1-GPU size: no faster, profiles/r6/ab/)
     coop = K == 1 and G * pad <= _COOP_MAX_ITEMS
-    return dict(K=K, rows=rows, pad=pad, period=period, coop=coop, pos=pos, sb=sb, nb=nb)
+    return FoldLayout(K=K, rows=rows, pad=pad, period=period, coop=coop, pos=pos, sb=sb, nb=nb)
 
 
-def _fold_items(lay: dict, Uall, Y, G: int, nq: int, out: dict):
+def _fold_items(lay: FoldLayout, Uall, Y, G: int, nq: int) -> Fold:
     """The GPU fold of the rows ``Uall`` (layout ``lay``) with the points
     -Y_q (affine, or uv(-Y_q) for the normalised lines), issued after the U
     combinations are queued (``Y`` may be the callable that issues their
-    inputs) -> out "fb", "blk", "sb", "nb"."""
+    inputs)."""
     dev = Uall.device
-    K, rows, pad, period, coop, pos = (lay[k] for k in ("K", "rows", "pad", "period", "coop", "pos"))
+    K, rows, pad, period, coop, pos = lay.K, lay.rows, lay.pad, lay.period, lay.coop, lay.pos
     UV = torch.zeros((period, 16), dtype=torch.int32, device=dev)
     if callable(Y):
         Y = Y()
@@ -1580,41 +1621,40 @@ def _fold_items(lay: dict, Uall, Y, G: int, nq: int, out: dict):
         UV.index_copy_(0, pos, negY.repeat(G, 1))
     with timers.span("rp.u.fold"):
         if coop:
-            out["fb"] = nt.rp_fold_accum_coop_raw(nt.rp_fold_coeffs(Uall), UV, Uall, period, 1)
+            fb = nt.rp_fold_accum_coop_raw(nt.rp_fold_coeffs(Uall), UV, Uall, period, 1)
         else:
-            out["fb"] = nt.rp_fold_accum_n(nt.rp_fold_ncoeffs(Uall), UV, Uall, period, 1, K)
-    out["blk"], out["sb"], out["nb"] = pad // rows, lay["sb"], lay["nb"]
+            fb = nt.rp_fold_accum_n(nt.rp_fold_ncoeffs(Uall), UV, Uall, period, 1, K)
+    return Fold(fb, pad // rows, lay.sb, lay.nb)
 
 
-def _fold_items_host(Uall, Y, G: int, nq: int, qoff, out: dict):
+def _fold_items_host(Uall, Y, G: int, nq: int, qoff) -> Fold:
     """Host: one Miller loop per pair (-Y_q, U_vq), rows v * nq + q."""
     if callable(Y):
         Y = Y()
     negY = nt.g1_to_affine(nt.g1_add(bn.g1_infinity_jac(nq, Uall.device), Y.contiguous(), subtract=True))
-    out["fb"] = torch.cat([nt.miller_loop(negY, Uall[v * nq:(v + 1) * nq].contiguous()) for v in range(G)])
-    out["blk"], out["sb"], out["nb"] = nq, qoff[:-1].tolist(), np.diff(qoff).tolist()
+    fb = torch.cat([nt.miller_loop(negY, Uall[v * nq:(v + 1) * nq].contiguous()) for v in range(G)])
+    return Fold(fb, nq, qoff[:-1].tolist(), np.diff(qoff).tolist())
 
 
-def _useg_items(msq: dict) -> torch.Tensor:
+def _useg_items(msq: UQueue) -> torch.Tensor:
     """Per-(VN, segment) U-side products of a key-grouped queue, on demand
     (a VN's batch failed: ``_segment_pass`` / ``_segment_hinted`` need them):
     the per-item fold over the retained U rows and -c_p y -> host [G, k, 96].
     After the final exponentiation they multiply to the grouped product."""
-    it, G = msq["items"], msq["G"]
-    Uall, nq, qoff = it["Uall"], it["nq"], it["qoff"]
-    out = {"G": G}
+    it, G = msq.items, msq.G
+    Uall, nq, qoff = it.Uall, it.nq, it.qoff
     if Uall.is_cuda:
         lay = _fold_layout(G, nq, np.diff(qoff), Uall.device)
-        pos = lay["pos"]
+        pos = lay.pos
         if pos is None:
-            pos = (torch.arange(G, device=Uall.device).view(G, 1) * lay["pad"]
+            pos = (torch.arange(G, device=Uall.device).view(G, 1) * lay.pad
                    + torch.arange(nq, device=Uall.device).view(1, nq)).reshape(-1)
-        U = torch.zeros((G * lay["pad"], 32), dtype=torch.int32, device=Uall.device)
+        U = torch.zeros((G * lay.pad, 32), dtype=torch.int32, device=Uall.device)
         U.index_copy_(0, pos, Uall)
-        _fold_items(lay, U, it["Y"], G, nq, out)
+        fold = _fold_items(lay, U, it.Y, G, nq)
     else:
-        _fold_items_host(Uall, it["Y"], G, nq, qoff, out)
-    return _seg_products(out)
+        fold = _fold_items_host(Uall, it.Y, G, nq, qoff)
+    return _seg_products(msq._replace(fold=fold))
 
 
 def _h2d(a, dev) -> torch.Tensor:
@@ -1644,11 +1684,11 @@ def _seg_all(flags: torch.Tensor, counts, dev) -> torch.Tensor:
     return bad == 0
 
 
-def _seg_products(msq: dict) -> torch.Tensor:
+def _seg_products(msq: UQueue) -> torch.Tensor:
     """Per-(VN, segment) products of the fold partials -> host [G, k, 96]:
     the blocks of every (VN, segment) gathered into one [blocks, G k] image
     (short segments padded with ones), 8-way device levels, then the host."""
-    fb, G, blk, sb, nb = msq["fb"], msq["G"], msq["blk"], msq["sb"], msq["nb"]
+    G, fb, blk, sb, nb = msq.G, msq.fold.fb, msq.fold.blk, msq.fold.sb, msq.fold.nb
     k = len(sb)
     dev = fb.device
     maxb = max(nb)
@@ -1691,64 +1731,38 @@ def _attribute_hinted(r: RangeProofList, segs: list, redo: list, x: dict) -> dic
             if got is not None:
                 out[v] = got
                 continue
-        out.update(_segment_pass(r, segs, [v], x))
+        out.update(_segment_pass(r, segs, [v], x).per)
         bad = [s for s, ok in enumerate(out[v]) if not ok]
         if hint is None and 0 < len(bad) < len(segs):
             hint = bad
     return out
 
 
-def _segment_hinted(r: RangeProofList, segs: list, v: int, T: list, x: dict):
+def _segment_hinted(r: RangeProofList, segs: list, v: int, T: list, x: FirstPass):
     """VN ``v``'s per-segment verdicts from the suspect segments ``T`` alone:
     the segment pass over T's proofs (same weights) gives T's per-segment
-    equation sides; the rest's sides are the first-pass totals minus T's --
-      lhs_rest = lhs_all / prod_T lhs_s,   e_rest = e_all - sum_T e_s,
-      D-check: dl_all - sum_T dl_s == dr_all - sum_T dr_s,
-      GT membership (when the first-pass combination failed): GGgam_all / prod_T GGgam_s
-    with R_all and every R_s, U_q of the rest in G2.  -> [bool] per segment,
-    or None when the rest fails or T's segments all pass (no attribution from
-    the hint: the caller runs the full pass)."""
-    dev = r.V.device
-    n, S, l, G = len(r), r.S, r.l, x["G"]
-    m, tot = n * S * l, x["tot"]
-    if tot["lhs"][v] is None or tot["dl"][v] is None:
-        return None
+    equation sides; the rest's sides are the first-pass totals without T's
+    (``Sides.rest``; GT membership, when the first-pass combination failed:
+    GGgam_all / prod_T GGgam_s) with R_all and every R_s, U_q of the rest in
+    G2.  -> [bool] per segment, or None when the rest fails or T's segments
+    all pass (no attribution from the hint: the caller runs the full pass)."""
     poff = np.cumsum([0] + list(segs))
     rT = rpl_cat([rpl_range(r, int(poff[s]), int(poff[s + 1])) for s in T])
-    pidx = torch.cat([torch.arange(int(poff[s]), int(poff[s + 1])) for s in T])
-    iidx = (pidx.view(-1, 1) * (S * l) + torch.arange(S * l).view(1, -1)).reshape(-1)
-    pidx, iidx = bn.h2d(pidx, dev), bn.h2d(iidx, dev)
-    sel = lambda t, w, idx: t.view(G, -1, w)[v].index_select(0, idx).contiguous()  # noqa: E731
-    Tt = bn.h2d(torch.tensor(T), x["u_seg"].device)
-    xT = dict(A2=x["A2"].index_select(0, torch.cat([iidx, iidx + m])), rho=sel(x["rho"], 8, iidx),
-              ab=sel(x["ab"], 2, iidx), gam=sel(x["gam"], 8, iidx), w=sel(x["w"], 8, pidx),
-              Cp=x["Cp"].index_select(0, pidx), z=x["z"].index_select(0, pidx),
-              useg=x["useg"][v: v + 1, T], u_seg=x["u_seg"][v: v + 1].index_select(1, Tt),
-              PB_base=x["PB_base"], gt_tab=x["gt_tab"], wc=x["wc"], G=1, m_first=[x["m_first"][v]])
-    comp = {}
-    perT = _segment_pass(rT, [segs[s] for s in T], [0], xT, comp)[0]
+    part = _segment_pass(rT, [segs[s] for s in T], [0], x.select(v, T, segs))
+    perT = part.per[0]
     if all(perT):
         return None
-    # the rest, from the totals
-    inv_lhs = nt.gt_inv(nt.gt_prod(comp["lhs"].view(len(T), 1, 96), chunk=64).view(1, 96))
-    lhs_rest = nt.gt_mul(tot["lhs"][v].view(1, 96), inv_lhs)
-    e_rest = tot["e"][v: v + 1].cpu()
-    for s_ in range(len(T)):
-        e_rest = nt.fr_arith(nt.FR_SUB, e_rest, comp["e"][s_: s_ + 1].contiguous())
-    eq = bool(nt.gt_eq(lhs_rest, nt.gt_fb_pow(x["gt_tab"], e_rest)).all())
-    d1 = nt.g1_sum(torch.cat([tot["dl"][v].view(1, 1, 24), comp["dr"].view(-1, 1, 24)]))
-    d2 = nt.g1_sum(torch.cat([tot["dr"][v].view(1, 1, 24), comp["dl"].view(-1, 1, 24)]))
-    d_ok = bool(nt.g1_eq(d1, d2)[0])
+    rest = x.tot.rest(v, part.sides, x.gt_tab)
     m_ok = True
-    if not x["m_first"][v]:
-        if comp.get("GGgam") is None:
+    if not x.m_first[v]:
+        if part.GGgam is None:
             return None
-        gi = nt.gt_inv(nt.gt_prod(comp["GGgam"].view(len(T), 1, 96), chunk=64).view(1, 96))
-        m_ok = _gt_in_subgroup(nt.gt_mul(tot["GGgam"][v: v + 1].cpu(), gi))
-    rest = [s for s in range(len(segs)) if s not in set(T)]
-    u_ok = bool(x["u_seg"][v].cpu()[rest].all()) if rest else True
-    g2_ok = tot["r_ok"][v] and all(comp["rok"]) and u_ok
-    if not (eq and d_ok and m_ok and g2_ok):
+        gi = nt.gt_inv(nt.gt_prod(part.GGgam.view(len(T), 1, 96), chunk=64).view(1, 96))
+        m_ok = _gt_in_subgroup_each(nt.gt_mul(x.GGgam[v: v + 1].contiguous(), gi))[0]
+    others = [s for s in range(len(segs)) if s not in set(T)]
+    u_ok = bool(x.u_seg[v].cpu()[others].all()) if others else True
+    g2_ok = x.r_ok[v] and all(part.rok) and u_ok
+    if not (rest.eq[0] and rest.d_ok[0] and m_ok and g2_ok):
         return None
     out = [True] * len(segs)
     for s_, s in enumerate(T):
@@ -1756,13 +1770,18 @@ def _segment_hinted(r: RangeProofList, segs: list, v: int, T: list, x: dict):
     return out
 
 
-def _segment_pass(r: RangeProofList, segs: list, redo: list, x: dict, comp: dict | None = None) -> dict:
+# ``_segment_pass``: "per" {vn: [bool] per segment}; rows (VN, segment): the closed "sides", "GGgam"
+# (prod a^gamma; None when no VN needed its own combination), "rok" (R_(v,s) in G2)
+SegmentPass = namedtuple("SegmentPass", "per sides GGgam rok")
+
+
+def _segment_pass(r: RangeProofList, segs: list, redo: list, x: FirstPass) -> SegmentPass:
     """Second, segment-grouped pass for the VNs ``redo`` whose batch failed:
     with the SAME weights, every side of the batch equation per (VN,
     segment) -- R MSM, prod a^rho, sum rho Zv, D-check, GT membership -- in
-    one grouped MSM / multi-exponentiation each; the U side's per-segment products come from
-    the first pass.  -> {vn: [bool] per segment}; ``comp`` receives the
-    per-(VN, segment) sides (host): lhs, e, dl, dr, GGgam (when computed), rok."""
+    one grouped MSM / multi-exponentiation each; the U side's per-segment
+    products come from the first pass; closed by ``_close`` as the first
+    pass is."""
     dev = r.V.device
     n, S, l = len(r), r.S, r.l
     m, nseg, Gf = n * S * l, len(segs), len(redo)
@@ -1774,7 +1793,7 @@ def _segment_pass(r: RangeProofList, segs: list, redo: list, x: dict, comp: dict
     def rows(t, w):
         return torch.cat([t[v * w:(v + 1) * w] for v in redo]) if Gf > 1 else t[redo[0] * w:(redo[0] + 1) * w]
 
-    rho, ab, w = rows(x["rho"], m), rows(x["ab"], m), rows(x["w"], n)
+    rho, ab, w = rows(x.rho, m), rows(x.ab, m), rows(x.w, n)
     # every input and every bucket plan (one host sync each) first, then the
     # device passes: a plan's sync then never waits behind another MSM's
     # queued passes (the first pass's schedule)
@@ -1789,62 +1808,49 @@ def _segment_pass(r: RangeProofList, segs: list, redo: list, x: dict, comp: dict
     # first-pass combination already bounds any non-GT component of the
     # whole batch (error ~2^-38.8), so its segments skip that 40% of the
     # multi-exponentiation
-    gam_groups = 2 if any(not x["m_first"][v] for v in redo) else 1
+    gam_groups = 2 if any(not x.m_first[v] for v in redo) else 1
     k = torch.zeros((gam_groups * Gf, 2 * m, 8), dtype=torch.int32, device=dev)
     abv = ab.view(Gf, m, 2)
     k[:Gf, :m, 0] = abv[:, :, 0]
     k[:Gf, m:, 0] = abv[:, :, 1]
     if gam_groups == 2:
-        k[Gf:, :m] = rows(x["gam"], m).view(Gf, m, 8)
+        k[Gf:, :m] = rows(x.gam, m).view(Gf, m, 8)
     k = k.view(-1, 8)
     fi2 = torch.arange(gam_groups * Gf, device=dev).view(gam_groups * Gf, 1)
     grp2 = (fi2 * nseg + iseg.repeat(2).view(1, 2 * m)).reshape(-1).to(torch.int32)
     # D-check per (v, s): sum w c C' - sum w D (groups (v, which, s))
-    wc = nt.fr_arith(nt.FR_MUL, w, r.challenge.contiguous())
-    dsc = torch.stack([wc.view(Gf, n, 8), w.view(Gf, n, 8)], 1).reshape(-1, 8).contiguous()
+    dpts, dsc = _dcheck_inputs(x.Cp, r.D, w, r.challenge, Gf)
     grp3 = ((fi.view(Gf, 1, 1) * 2 + torch.arange(2, device=dev).view(1, 2, 1)) * nseg
             + pseg.view(1, 1, n)).reshape(-1).to(torch.int32)
-    dpts = torch.cat([x["Cp"].contiguous(), r.D.contiguous()]).repeat(Gf, 1)
     with timers.span("rp.seg.plans"):
         hR = nt.g2_msm_launch(r.V, s_r, grp, K, c=_seg_c(Gf * m, K))
-        mplan = nt.multi_exp_plan(k, grp2, gam_groups * K, W=x["wc"][0], c=x["wc"][1])
+        mplan = nt.multi_exp_plan(k, grp2, gam_groups * K, W=x.wc[0], c=x.wc[1])
         dplan = nt.g1_msm_plan(dsc, grp3, 2 * K)
     with timers.span("rp.seg.passes"):
         S_R = nt.g2_msm_run(r.V, hR)
-        mexp = nt.multi_exp_grouped(x["A2"], k, grp2, gam_groups * K, W=x["wc"][0], c=x["wc"][1], plan=mplan)
+        mexp = nt.multi_exp_grouped(x.A2, k, grp2, gam_groups * K, W=x.wc[0], c=x.wc[1], plan=mplan)
         dh = nt.g1_msm_launch(dpts, dsc, grp3, 2 * K, bits=256, plan=dplan)
     # sum rho Zv, sum w Zr, sum w z per (v, s): per-proof sums, then per-segment
     offs = torch.from_numpy((np.arange(Gf).reshape(Gf, 1) * n + poff[:-1].reshape(1, nseg)).reshape(-1))
     offs = bn.h2d(torch.cat([offs, torch.tensor([Gf * n])]), dev)
     e = nt.fr_seg_sum(nt.fr_dot_rows(rho, r.zv.repeat(Gf, 1).contiguous(), Gf * n), offs)
     dzr = nt.fr_seg_sum(nt.fr_arith(nt.FR_MUL, w, r.zr.contiguous()), offs)
-    dz = nt.fr_seg_sum(nt.fr_arith(nt.FR_MUL, w, x["z"].contiguous()), offs)
+    dz = nt.fr_seg_sum(nt.fr_arith(nt.FR_MUL, w, x.z.contiguous()), offs)
     # host: Horner steps, Miller loops of B with each R_(v,s), final exps
     with timers.span("rp.seg.gt_finish"):
         GG = nt.multi_exp_grouped_finish(mexp)                         # [gam_groups * K, 96]
         m_ok = _gt_in_subgroup_each(GG[K:]) if gam_groups == 2 else [True] * K
-    if comp is not None and gam_groups == 2:
-        comp["GGgam"] = GG[K:].cpu()
-    GG = GG[:K]
+    GGgam = GG[K:].cpu() if gam_groups == 2 else None
     with timers.span("rp.seg.r_finish"):
         fR, rok = _msm_r_miller(hR, S_R)
     with timers.span("rp.seg.d_finish"):
         D_all = nt.g1_msm_finish(dh).view(Gf, 2, nseg, 24)
-    e, dzr, dz = e.cpu(), dzr.cpu(), dz.cpu()
-    useg = torch.stack([x["useg"][v] for v in redo]).view(K, 96)
-    useg_ok = x["u_seg"].cpu()[redo].reshape(-1).tolist()
-    lhs = nt.gt_mul(nt.final_exp(nt.gt_mul(useg.contiguous(), fR.contiguous())), GG.contiguous())
-    eq = nt.gt_eq(lhs, nt.gt_fb_pow(x["gt_tab"], e)).tolist()
-    PB = nt.g1_mul(x["PB_base"].repeat(K, 1), torch.stack([dzr, dz], 1).reshape(-1, 8).contiguous()).view(K, 2, 24)
-    lhs_d = nt.g1_sum(torch.stack([D_all[:, 0].reshape(K, 24), PB[:, 0], PB[:, 1]]).contiguous())
-    d_ok = nt.g1_eq(lhs_d.contiguous(), D_all[:, 1].reshape(K, 24).contiguous()).tolist()
-    if comp is not None:
-        comp.update(lhs=lhs, e=e, dl=lhs_d, dr=D_all[:, 1].reshape(K, 24), rok=rok)
-    out = {}
-    for f, v in enumerate(redo):
-        out[v] = [bool(eq[f * nseg + s_]) and bool(d_ok[f * nseg + s_]) and bool(useg_ok[f * nseg + s_])
-                  and bool(rok[f * nseg + s_]) and m_ok[f * nseg + s_] for s_ in range(nseg)]
-    return out
+    useg = torch.stack([x.useg[v] for v in redo]).view(K, 96)
+    sides = _close(nt.gt_mul(useg.contiguous(), fR.contiguous()), GG[:K], e.cpu(),
+                   D_all.transpose(1, 2).reshape(K, 2, 24), torch.stack([dzr.cpu(), dz.cpu()], 1), x.PB_base, x.gt_tab)
+    useg_ok = x.u_seg.cpu()[redo].reshape(-1).tolist()
+    ok = [sides.eq[i] and sides.d_ok[i] and bool(useg_ok[i]) and rok[i] and m_ok[i] for i in range(K)]
+    return SegmentPass({v: ok[f * nseg:(f + 1) * nseg] for f, v in enumerate(redo)}, sides, GGgam, rok)
 
 
 def _msm_r_miller(hR, S_dev) -> torch.Tensor:
@@ -1924,12 +1930,6 @@ def rpl_range(r: RangeProofList, a: int, b: int) -> RangeProofList:
     sl = lambda t, w: None if t is None else t[a * w: b * w]  # noqa: E731
     return RangeProofList(r.u, l, S, r.offset[a:b], r.cols[a:b], r.commit[a:b], sl(r.challenge, 1), sl(r.zr, 1),
                           sl(r.D, 1), sl(r.zphi, l), sl(r.zv, S * l), sl(r.V, S * l), sl(r.A, S * l))
-
-
-def _slice(r: RangeProofList, k: int) -> RangeProofList:
-    l, S = r.l, r.S
-    return RangeProofList(r.u, l, S, r.offset[:k], r.cols[:k], r.commit[:k], r.challenge[:k], r.zr[:k], r.D[:k],
-                          r.zphi[: k * l], r.zv[: k * S * l], r.V[: k * S * l], r.A[: k * S * l])
 
 
 def verify_range_proof_single_reference(rpl: RangeProofList, p: int, sigmat: SigMaterial, P_point) -> bool:

@@ -279,18 +279,10 @@ def test_verifier_accepts_and_rejects(device, proofs):
     assert rp.verify_range_proof_list_multi(bad, sm, P, 2, dev) == [False] * 2
 
 
-@pytest.mark.parametrize("device", DEVICES)
-@pytest.mark.parametrize("field", ["V", "zr", "A", "A_off_gt"])
-def test_segment_attribution(device, field, proofs, monkeypatch):
-    """segs = per-request slices: a clean batch clears every segment; a
-    tampered proof is named by the failing VN's segment-grouped second pass
-    (pairing side: V; D-equation: Zr; GT side: A), the other segments pass."""
-    dev = _dev(device)
-    rpl, sm, P = proofs
-    r = rpl.to(dev)
-    assert rp.verify_range_proof_list_multi(r, sm, P, 2, dev, segs=[1, 2, 1]) == [[True] * 3] * 2
+def _tamper(rpl, dev, field):
+    """One false proof in the ``proofs`` list -> (the list, the per-segment verdicts of segs=[1, 2, 1])."""
     bad = rpl.to(dev)
-    n, l, S = len(bad), bad.l, bad.S
+    l, S = bad.l, bad.S
     if field == "V":                                      # proof 2 (segment 1): a valid G2 point, wrong item
         V = bad.V.clone()
         V[2 * S * l] = V[2 * S * l + 1]
@@ -311,6 +303,20 @@ def test_segment_attribution(device, field, proofs, monkeypatch):
         A[-1, -1] ^= 1
         bad.A = A
         want = [True, True, False]
+    return bad, want
+
+
+@pytest.mark.parametrize("device", DEVICES)
+@pytest.mark.parametrize("field", ["V", "zr", "A", "A_off_gt"])
+def test_segment_attribution(device, field, proofs, monkeypatch):
+    """segs = per-request slices: a clean batch clears every segment; a
+    tampered proof is named by the failing VN's segment-grouped second pass
+    (pairing side: V; D-equation: Zr; GT side: A), the other segments pass."""
+    dev = _dev(device)
+    rpl, sm, P = proofs
+    r = rpl.to(dev)
+    assert rp.verify_range_proof_list_multi(r, sm, P, 2, dev, segs=[1, 2, 1]) == [[True] * 3] * 2
+    bad, want = _tamper(rpl, dev, field)
     decodes = field != "A_off_gt"
     calls, hinted = [], []
     orig, orig_h = rp._segment_pass, rp._segment_hinted
@@ -323,6 +329,76 @@ def test_segment_attribution(device, field, proofs, monkeypatch):
     assert len(calls) == (3 if decodes else 0)       # one full pass + each hinted VN's pass over T
     assert len(hinted) == (2 if decodes else 0) and all(h == want for h in hinted)
     assert rp.verify_range_proof_list_multi(bad, sm, P, 2, dev) == [False] * 2
+
+
+def _captured_close(monkeypatch):
+    """[(arguments, Sides)] of every ``rp._close`` from here on."""
+    calls, orig = [], rp._close
+
+    def close(*a):
+        calls.append((a, orig(*a)))
+        return calls[-1][1]
+
+    monkeypatch.setattr(rp, "_close", close)
+    return calls
+
+
+@pytest.mark.parametrize("device", DEVICES)
+@pytest.mark.parametrize("field", ["V", "zr"])
+def test_segment_sides_multiply_to_the_total(device, field, proofs, monkeypatch):
+    """What the hinted attribution rests on: the sides of a VN's segments,
+    closed by the segment pass, multiply / add up to the sides of its whole
+    batch, closed by the first pass -- on the pairing side (V) and on the
+    D-equation (Zr), where the other comparison holds throughout."""
+    dev = _dev(device)
+    rpl, sm, P = proofs
+    bad, want = _tamper(rpl, dev, field)
+    calls = _captured_close(monkeypatch)
+    assert rp.verify_range_proof_list_multi(bad, sm, P, 3, dev, segs=[1, 2, 1]) == [want] * 3
+    tot, seg = calls[0][1], calls[1][1]                   # the 3 VNs; VN 0's 3 segments
+    assert tot.lhs.shape[0] == 3 and seg.lhs.shape[0] == 3
+    assert bool(nt.gt_eq(nt.gt_prod(seg.lhs.view(3, 1, 96)), tot.lhs[0:1].contiguous()).all())
+    assert torch.equal(nt.fr_seg_sum(seg.e.contiguous(), torch.tensor([0, 3])), tot.e[0:1])
+    assert bool(nt.g1_eq(nt.g1_sum(seg.dl.view(3, 1, 24)), tot.dl[0:1].contiguous()).all())
+    assert bool(nt.g1_eq(nt.g1_sum(seg.dr.view(3, 1, 24)), tot.dr[0:1].contiguous()).all())
+    if field == "V":
+        assert not tot.eq[0] and tot.d_ok[0] and seg.eq == want and seg.d_ok == [True] * 3
+    else:
+        assert tot.eq[0] and not tot.d_ok[0] and seg.eq == [True] * 3 and seg.d_ok == want
+
+
+@pytest.mark.parametrize("device", DEVICES)
+def test_close_rows_are_independent(device, proofs, monkeypatch):
+    """``_close`` row by row gives what the K-row call gives, and a changed
+    exponent sum fails the pairing equation of its own row only."""
+    dev = _dev(device)
+    rpl, sm, P = proofs
+    bad, want = _tamper(rpl, dev, "V")
+    calls = _captured_close(monkeypatch)
+    assert rp.verify_range_proof_list_multi(bad, sm, P, 3, dev, segs=[1, 2, 1]) == [want] * 3
+    (F, GG, e, D, dd, PB_base, gt_tab), seg = calls[1]
+    assert F.shape[0] == 3 and seg.eq == want
+    for i in range(3):
+        one = rp._close(F[i:i + 1], GG[i:i + 1], e[i:i + 1], D[i:i + 1], dd[i:i + 1], PB_base, gt_tab)
+        assert torch.equal(one.lhs, seg.lhs[i:i + 1])
+        assert one.eq == seg.eq[i:i + 1] and one.d_ok == seg.d_ok[i:i + 1]
+        assert bool(nt.g1_eq(one.dl, seg.dl[i:i + 1].contiguous()).all())
+    e2 = e.clone()
+    e2[0, 0] ^= 1                                         # e +- 1 in row 0, whose equation held
+    alt = rp._close(F, GG, e2, D, dd, PB_base, gt_tab)
+    assert alt.eq == [False] + seg.eq[1:] and alt.d_ok == seg.d_ok and torch.equal(alt.lhs, seg.lhs)
+
+
+@pytest.mark.parametrize("device", DEVICES)
+@pytest.mark.parametrize("field", ["V", "zr", "A", "A_off_gt"])
+def test_hint_changes_no_verdict(device, field, proofs, monkeypatch):
+    """The verdicts with the hinted attribution are those of the full segment pass per VN."""
+    dev = _dev(device)
+    rpl, sm, P = proofs
+    bad, want = _tamper(rpl, dev, field)
+    hinted = rp.verify_range_proof_list_multi(bad, sm, P, 3, dev, segs=[1, 2, 1])
+    monkeypatch.setattr(rp, "_segment_hinted", lambda *a: None)
+    assert rp.verify_range_proof_list_multi(bad, sm, P, 3, dev, segs=[1, 2, 1]) == hinted == [want] * 3
 
 
 @pytest.mark.parametrize("device", DEVICES)

@@ -224,11 +224,11 @@ def test_grouped_product_matches_per_item(device, proofs, segs, monkeypatch):
     S_R, hR = nt.g2_msm_device(r.V, s_r, m, ((m, 254),) * G, c=rp._r_window(m, G))
     fR, _ = rp._msm_r_miller(hR, S_R)
     kg = rp._key_groups(r.cols, S, sm.n_cols, dev)
-    assert kg["ng"] == 6 and sorted(kg["len"].tolist()) == [1, 1, 1, 1, 2, 2]
+    assert kg.ng == 6 and sorted(kg.len.tolist()) == [1, 1, 1, 1, 2, 2]
     yg = dict(groups=kg, challenge=r.challenge, y_jac=sm.y_jac.to(dev))
     q = rp._msm_queue(Y, r.V, ab, G, n, S, l, None, segs, ygroup=yg)
     k = len(segs) if segs else 1
-    assert q["sb"] == [0] and tuple(q["u_seg"].shape) == (G, k) and bool(q["u_seg"].all())
+    assert q.fold.sb == [0] and tuple(q.u_seg.shape) == (G, k) and bool(q.u_seg.all())
     Fg = rp._seg_products(q)                                  # the per-VN product only
     assert tuple(Fg.shape) == (G, 1, 96)
     useg = rp._useg_items(q)

@@ -63,10 +63,9 @@ tU = nt.g2_joint_table(U, sgn)
 
 def fold(rows_U, Y, npairs):
     lay = rp._fold_layout(G, npairs, np.array([npairs]), dev)
-    Ul = torch.zeros((G * lay["pad"], 32), dtype=torch.int32, device=dev)
-    Ul.view(G, lay["pad"], 32)[:, :npairs] = rows_U.view(G, -1, 32)[:, :npairs]
-    out = {}
-    return timed(lambda: rp._fold_items(lay, Ul, Y, G, npairs, out)), lay["K"], lay["coop"]
+    Ul = torch.zeros((G * lay.pad, 32), dtype=torch.int32, device=dev)
+    Ul.view(G, lay.pad, 32)[:, :npairs] = rows_U.view(G, -1, 32)[:, :npairs]
+    return timed(lambda: rp._fold_items(lay, Ul, Y, G, npairs)), lay.K, lay.coop
 
 
 res["t_fold_items"], res["K_items"], _ = fold(U, Yall, nq)
