@@ -141,6 +141,7 @@ _SIGS = {
     "dx_rp_coeffs": [_P, _P, _P, _L],
     "dx_int_moments": [_I, _P, _P, _L, _I, _P, _L, _P, _I, _P, _P],
     "dx_extreme_digit_bits": [_I, _P, _P, _L, _P, _L, _P, _L, _I, _L, _L, _L, _L, _L, _L, _P, _P],
+    "dx_digit_histogram": [_I, _P, _P, _L, _P, _L, _P, _L, _L, _L, _L, _L, _L, _L, _P, _P],
     "dx_sha256_rows": [_I, _P, _P, _L, _L, _L, _L, _P],
     "dx_sha256_segments": [_I, _P, _P, _L, _L, _L, _P],
     "dx_g1_aff_to_uv": [_I, _P, _P, _L],
@@ -1111,16 +1112,17 @@ def _upload(a: np.ndarray, device) -> torch.Tensor:
     return t
 
 
-def _tile_plan(counts: np.ndarray):
+def _tile_plan(counts: np.ndarray, min_rows: int = 64):
     """Host-made tile plan of the segmented reductions: ``([n_tiles, 3] int64
     rows (segment, row0, row1), [G + 1] first tile of every segment)``.  Tiles
     are row ranges of one segment, sized so a big DP spreads over ~2k
-    workgroups and each tile still streams >= 64 rows; a segment's tiles are
-    consecutive and an empty segment has none."""
+    workgroups and each tile still streams >= max(64, ``min_rows``) rows
+    (rounded up to a multiple of 64; a segment's last tile may be shorter); a
+    segment's tiles are consecutive and an empty segment has none."""
     G = len(counts)
     if G == 0:
         return np.zeros((0, 3), dtype=np.int64), np.zeros(1, dtype=np.int64)
-    per_tile = -(-int(counts.sum()) // 2048)
+    per_tile = max(int(min_rows), -(-int(counts.sum()) // 2048))
     chunk = max(64, (per_tile + 63) // 64 * 64)
     per = np.maximum(1, -(-counts // chunk)) * (counts > 0)
     seg = np.repeat(np.arange(G, dtype=np.int64), per)
@@ -1209,6 +1211,59 @@ def extreme_digit_bits(Z: torch.Tensor, seg_rows, is_max: bool, qmin: int, qmax:
     _call("dx_extreme_digit_bits", g, s, _ptr(Z, strided=True), Z.stride(0) if Z.shape[0] > 1 else 1,
           _ptr(desc[: 3 * n_tiles]), n_tiles, _ptr(desc[3 * n_tiles:]), G, 1 if is_max else 0, qmin, qmax, base,
           base ** (L - k), base ** (L - 1 - k), prefix, _ptr(partial), _ptr(out))
+    return out
+
+
+DIGIT_HIST_MAX_BASE = 4096
+DIGIT_HIST_MAX_RANGE = 1 << 40
+
+
+def digit_histogram(Z: torch.Tensor, seg_rows, qmin: int, qmax: int, base: int, round: int,
+                    prefix: int) -> torch.Tensor:
+    """K14c (csrc/kernels/dx_digit_hist.hip): the [G, base] int64 counts every DP
+    of a batch encrypts in round ``round`` of the iterative frequencyCount (the
+    rounds of a quantile search).
+
+    Z [rows, n_in] holds the DPs' records back to back (``seg_rows[g]`` rows for
+    DP g; only column 0 is read, through Z's row stride).  With R = qmax - qmin
+    + 1 and L the smallest integer with base^L >= R, a record x of DP g inside
+    [qmin, qmax] has o = x - qmin and counts in bin (o div base^(L-1-round)) mod
+    base iff o div base^(L-round) == prefix; records outside the domain are
+    dropped.  Two launches for all DPs (per-tile LDS histograms, then the sum
+    over each DP's tiles); the tile plan is int_moments' with tiles of at least
+    ``base`` rows."""
+    assert Z.dtype == torch.int64 and Z.dim() == 2
+    qmin, qmax, base, k, prefix = int(qmin), int(qmax), int(base), int(round), int(prefix)
+    R = qmax - qmin + 1
+    if not 2 <= base <= DIGIT_HIST_MAX_BASE or not 1 <= R <= DIGIT_HIST_MAX_RANGE:
+        raise ValueError(f"digit_histogram: base {base}, {R} values")
+    L, p = 1, base
+    while p < R:
+        p *= base
+        L += 1
+    if not 0 <= k < L or not 0 <= prefix < base ** k:
+        raise ValueError(f"digit_histogram: round {k} of {L}, prefix {prefix}")
+    counts = np.asarray(seg_rows, dtype=np.int64).reshape(-1)
+    G = len(counts)
+    if counts.sum() != Z.shape[0] or (G and counts.min() < 0):
+        raise ValueError(f"digit_histogram: segments cover {counts.sum()} rows, Z has {Z.shape[0]}")
+    if Z.shape[0] and Z.shape[1] < 1:
+        raise ValueError("digit_histogram: Z has no column")
+    out = torch.empty((G, base), dtype=torch.int64, device=Z.device)
+    if G == 0:
+        return out
+    plan, first = _tile_plan(counts, base)
+    n_tiles = len(plan)
+    if n_tiles and int((plan[:, 2] - plan[:, 1]).max()) >= 1 << 31:
+        raise ValueError("digit_histogram: a tile of 2^31 rows or more")
+    # one upload: the tiles, then every DP's tile range
+    desc = _upload(np.concatenate([plan.reshape(-1), first]), Z.device)
+    partial = torch.empty((max(1, n_tiles), base), dtype=torch.int64, device=Z.device)
+    g, s = _ctx(out)
+    # (Z is read in place: a view's row stride is the kernel's ldz)
+    _call("dx_digit_histogram", g, s, _ptr(Z, strided=True), Z.stride(0) if Z.shape[0] > 1 else 1,
+          _ptr(desc[: 3 * n_tiles]), n_tiles, _ptr(desc[3 * n_tiles:]), G, qmin, qmax, base, base ** (L - k),
+          base ** (L - 1 - k), prefix, _ptr(partial), _ptr(out))
     return out
 
 

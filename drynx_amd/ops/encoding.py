@@ -249,6 +249,46 @@ def encode_extreme_digit(data, operation: Operation, base: int, rnd: int, prefix
     return encode_bits([v == 0 for v in vals], pk, "and", with_proofs, ranges)  # values are the inverted AND bits
 
 
+def digit_histogram_values(operation: Operation, Z: torch.Tensor, seg_rows, base: int, rnd: int,
+                           prefix: int) -> torch.Tensor:
+    """[n_dp, base] int64 counts of one round of the iterative frequencyCount
+    (the rounds of a quantile search): per DP the histogram of the
+    base-``base`` digit ``rnd`` of its in-domain records whose leading digits
+    equal ``prefix``; records outside the domain are dropped as the one-shot
+    histogram drops them.  Two launches for every DP of the batch
+    (``native.digit_histogram``); the host path runs the same entry."""
+    from .. import native as nt
+
+    if operation.NameOp != "frequencyCount":
+        raise ValueError(f"{operation.NameOp} has no digit histogram")
+    return nt.digit_histogram(Z, seg_rows, operation.QueryMin, operation.QueryMax, base, rnd, prefix)
+
+
+def encode_digit_histogram(data, operation: Operation, base: int, rnd: int, prefix: int, pk, with_proofs=False,
+                           ranges=None):
+    """One DP's response to a round of the iterative frequencyCount: the counts
+    of ``digit_histogram_values`` for its records, encrypted as integers like
+    ``encode_frequency_count``'s."""
+    x = _t(data[0], pk.device).reshape(-1).to(torch.int64)
+    vals = digit_histogram_values(operation, x[:, None], [x.numel()], base, rnd, prefix)[0].cpu().tolist()
+    return _encrypt_with_proofs(pk, vals, with_proofs, ranges)
+
+
+def iterative_values(operation: Operation, Z: torch.Tensor, seg_rows, base: int, rnd: int, prefix: int):
+    """The values of one round of an iterative query, by operation."""
+    if operation.NameOp == "frequencyCount":
+        return digit_histogram_values(operation, Z, seg_rows, base, rnd, prefix)
+    return extreme_digit_values(operation, Z, seg_rows, base, rnd, prefix)
+
+
+def encode_iterative(data, operation: Operation, base: int, rnd: int, prefix: int, pk, with_proofs=False,
+                     ranges=None):
+    """One DP's response to one round of an iterative query, by operation."""
+    if operation.NameOp == "frequencyCount":
+        return encode_digit_histogram(data, operation, base, rnd, prefix, pk, with_proofs, ranges)
+    return encode_extreme_digit(data, operation, base, rnd, prefix, pk, with_proofs, ranges)
+
+
 def encrypt_batch(pk: eg.PublicKeyTable, values: torch.Tensor, bits: bool):
     """One encryption launch for a whole batch: ints (EncryptIntVectorGetRs),
     or for bit encodings without proofs a fresh random non-zero scalar where the

@@ -50,7 +50,7 @@ def _seed(survey_id: str, dp_id: str) -> int:
 
 def data_seed_id(sq) -> str:
     """The id a DP's generated records are seeded from: the survey's, or for a
-    round of an iterative min/max the id its rounds share (every round has a
+    round of an iterative query the id its rounds share (every round has a
     survey id of its own and must still see the same records)."""
     return sq.IterSurveyID if sq.IterBase else sq.SurveyID
 
@@ -116,8 +116,8 @@ def dp_encode(ctx, sq, dp, sync_timer: bool = True) -> dict:
     with timers.timed(f"{dp.id}_DPencoding", sync=sync_timer):
         for _ in groups:
             if sq.IterBase:
-                r = enc.encode_extreme_digit(data, op, sq.IterBase, sq.IterRound, sq.IterPrefix, pk, with_proofs,
-                                             q.Ranges)
+                # min/max: the unary digit of the extreme; frequencyCount: the digit's histogram
+                r = enc.encode_iterative(data, op, sq.IterBase, sq.IterRound, sq.IterPrefix, pk, with_proofs, q.Ranges)
             else:
                 r = enc.encode(data, pk, op_eff, ranges=q.Ranges, with_proofs=with_proofs, lr_data=lr)
             cv = r.cv
@@ -172,8 +172,8 @@ def dp_encode_batch(ctx, sq, dps: list) -> dict:
             Z = Z.pin_memory().to(device, non_blocking=True)
     else:
         Z = torch.cat([m.to(device) for m in mats]).contiguous()
-    if sq.IterBase:  # one round of the iterative min/max: [n_dp, IterBase] from the K14b kernel pair
-        vals = enc.extreme_digit_values(op, Z, rows, sq.IterBase, sq.IterRound, sq.IterPrefix)
+    if sq.IterBase:  # one round of an iterative query: [n_dp, IterBase] from the K14b (min/max) or K14c (counts) pair
+        vals = enc.iterative_values(op, Z, rows, sq.IterBase, sq.IterRound, sq.IterPrefix)
     else:
         vals = enc.batch_values(op.NameOp, Z, rows, op.QueryMin, op.QueryMax)  # [n_dp, n_out]
     return _encode_batch_tail(ctx, sq, dps, vals, groups, pk)

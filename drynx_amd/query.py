@@ -196,6 +196,9 @@ class SurveyQuery:
     # neutral value otherwise (csrc/kernels/dx_extreme.hip).  IterSurveyID is
     # the id the rounds of one search share: generated records are seeded from
     # it, so every round sees the same data.  0 = the reference's one-shot query.
+    # A frequencyCount round (the rounds of a quantile search) answers with the
+    # b counts of that digit among the DP's in-domain records under the prefix
+    # (csrc/kernels/dx_digit_hist.hip).
     IterBase: int = 0
     IterRound: int = 0
     IterPrefix: int = 0
@@ -389,7 +392,9 @@ def check_parameters(sq: SurveyQuery, diffp: bool) -> bool:
 
 
 ITER_MAX_BASE = 65536
+ITER_MAX_HIST_BASE = 4096  # frequencyCount rounds: one LDS counter per output (csrc/kernels/dx_digit_hist.hip)
 ITER_MAX_RANGE = 1 << 40  # every power of the base a round divides by stays far inside int64
+ITER_OPERATIONS = ("min", "max", "frequencyCount")
 
 
 def iter_rounds(qmin: int, qmax: int, base: int) -> int:
@@ -416,10 +421,12 @@ def _check_iterative(sq: SurveyQuery) -> list:
     q = sq.Query
     op = q.Operation
     msg = []
-    if not isinstance(b, int) or isinstance(b, bool) or not 2 <= b <= ITER_MAX_BASE:
-        return [f"iterative base outside 2..{ITER_MAX_BASE}"]
-    if op.NameOp not in ("min", "max"):
-        msg.append("iterative rounds are defined for min and max only")
+    hist = op.NameOp == "frequencyCount"
+    top = ITER_MAX_HIST_BASE if hist else ITER_MAX_BASE
+    if not isinstance(b, int) or isinstance(b, bool) or not 2 <= b <= top:
+        return [f"iterative base outside 2..{top}"]
+    if op.NameOp not in ITER_OPERATIONS:
+        msg.append("iterative rounds are defined for min, max and frequencyCount only")
     if q.CuttingFactor != 0:
         msg.append("iterative rounds with a cutting factor")
     if add_diff_p(q.DiffP):
@@ -435,7 +442,13 @@ def _check_iterative(sq: SurveyQuery) -> list:
             msg.append("iterative prefix is not a number of IterRound digits")
     if op.NbrOutput != b:
         msg.append("an iterative round has exactly IterBase outputs")
-    if q.Proofs and (q.Ranges is None or not _ranges_bits(q.Ranges)):
+    if hist:
+        # counts, not bits: any range wide enough for a DP's records, one per output
+        if q.Proofs and (q.Ranges is None or len(q.Ranges) < b):
+            msg.append("an iterative frequencyCount round with proofs needs IterBase ranges")
+        elif q.Proofs and not _ranges_zeros(q.Ranges) and any(r[0] == 0 and r[1] == 0 for r in q.Ranges):
+            msg.append("an iterative frequencyCount round with (0, 0) among other ranges")
+    elif q.Proofs and (q.Ranges is None or not _ranges_bits(q.Ranges)):
         msg.append("iterative rounds with proofs need (2, 1) ranges")
     return msg
 
@@ -484,9 +497,10 @@ def choose_operation(name: str, query_min: int, query_max: int, d: int, cutting_
 
 
 def iter_operation(name: str, query_min: int, query_max: int, base: int) -> Operation:
-    """The operation of one round of the iterative min/max (extension): the
-    full domain stays in QueryMin/QueryMax, the DPs send ``base`` unary outputs."""
-    if name not in ("min", "max"):
+    """The operation of one round of an iterative query (extension): the full
+    domain stays in QueryMin/QueryMax, the DPs send ``base`` outputs (unary
+    bits for min/max, the digit's counts for frequencyCount)."""
+    if name not in ITER_OPERATIONS:
         raise ValueError(f"Operation: <{name}> has no iterative rounds")
     iter_rounds(query_min, query_max, base)
     return Operation(NameOp=name, NbrInput=1, NbrOutput=int(base), QueryMin=int(query_min), QueryMax=int(query_max))

@@ -97,9 +97,9 @@ class DrynxClient:
 
     # ------------------------------------------------------------------ iterative min / max
     def iterative_round_query(self, sq: SurveyQuery, base: int, k: int, prefix: int, iter_id: str) -> SurveyQuery:
-        """Round ``k`` of the iterative min/max search ``iter_id`` as a survey of
-        its own: a copy of ``sq`` (a ``min``/``max`` survey over the full domain)
-        with ``base`` outputs, the first ``base`` columns of its ranges and
+        """Round ``k`` of the iterative search ``iter_id`` as a survey of its own:
+        a copy of ``sq`` (a ``min``/``max``/``frequencyCount`` survey over the full
+        domain) with ``base`` outputs, the first ``base`` columns of its ranges and
         input-validation signatures (the same objects every round, so the
         provers' and verifiers' tables built for round 0 serve the others) and
         a survey id derived from ``iter_id``."""
@@ -195,6 +195,79 @@ class DrynxClient:
             raise RuntimeError(f"iterative {op.NameOp} {iter_id}: {failed}")
         return float(op.QueryMin + (0 if empty else prefix)), rounds
 
+    # ------------------------------------------------------------------ iterative quantiles
+    def send_iterative_quantile(self, sq: SurveyQuery, base: int, num: int, den: int, on_round=None):
+        """Iterative quantile (extension): the ``num/den`` nearest-rank quantile of
+        the records the ``frequencyCount`` survey ``sq`` counts, found one
+        base-``base`` digit per round, most significant first.  Every round is
+        an ordinary verifiable query whose ``base`` outputs are the counts of
+        that digit among the records under the prefix found so far (its own
+        survey id, proofs and block).  Round 0 gives the number N of records in
+        the domain and the target rank t = max(1, ceil(num * N / den)): 0/1 is
+        the minimum, 1/1 the maximum, 1/2 the lower median.  Each round takes
+        the first digit whose cumulative count reaches t and carries the rest
+        of the rank into the chosen bin.  Returns ``(value, rounds)``: the
+        quantile and every round's SurveyResult (``client_out`` = the counts
+        per group).  ``on_round(k, digit, result)`` is called after each round.
+        Raises when a round's total is not the count of the bin chosen in the
+        round before, the groups disagree, or no DP has a record in the domain."""
+        num, den = int(num), int(den)
+        if den < 1 or not 0 <= num <= den:
+            raise ValueError(f"no quantile {num}/{den}")
+        op = sq.Query.Operation
+        if op.NameOp != "frequencyCount":
+            raise ValueError(f"an iterative quantile runs on a frequencyCount survey, not {op.NameOp}")
+        L = iter_rounds(op.QueryMin, op.QueryMax, base)
+        iter_id = sq.SurveyID or new_survey_id()
+        collective = getattr(getattr(self.entry, "comm", None), "world", 1) > 1
+        round_op = iter_operation(op.NameOp, op.QueryMin, op.QueryMax, base)
+
+        def counts(partial):
+            """Per group the round's aggregate counts, decoded as the one-shot frequencyCount's."""
+            with timers.timed("Decode"):
+                return [[int(round(v)) for v in self.decode(cv.to(self.device), round_op)] for cv in partial.groups()]
+
+        # With several ranks the others serve exactly L rounds (``serve_iterative``):
+        # a search that has failed, or found no record, still runs them all.
+        prefix, rounds, failed, empty, t, chosen = 0, [], None, False, 0, 0
+        for k in range(L):
+            rq = self.iterative_round_query(sq, base, k, prefix, iter_id)
+            if k == 0 and not check_parameters(rq, False):
+                raise ValueError("the iterative query fails CheckParameters")
+            res = self.entry.run_survey(rq, on_result=counts)
+            rounds.append(res)
+            cs = res.client_out
+            c, digit = cs[0], 0
+            if failed is None and not empty:
+                total = sum(c)
+                if any(x != c for x in cs):
+                    failed = f"round {k}: the groups disagree on the counts"
+                elif k == 0 and total == 0:
+                    empty = True
+                elif k == 0:
+                    t = max(1, (num * total + den - 1) // den)
+                elif total != chosen:
+                    failed = (f"round {k}: {total} records under the prefix {prefix}, round {k - 1} counted "
+                              f"{chosen}: an answer changed between rounds")
+            if (failed is not None or empty) and not collective:
+                break
+            if failed is None and not empty:
+                below = 0
+                for digit, x in enumerate(c):  # the smallest digit whose cumulative count reaches t
+                    if below + x >= t:
+                        break
+                    below += x
+                t -= below
+                chosen = c[digit]
+            if on_round is not None:
+                on_round(k, digit, res)
+            prefix = prefix * base + digit
+        if failed is not None:
+            raise RuntimeError(f"iterative quantile {iter_id}: {failed}")
+        if empty:
+            raise RuntimeError(f"iterative quantile {iter_id}: no records in the domain")
+        return float(op.QueryMin + prefix), rounds
+
     # ------------------------------------------------------------------ VN / skipchain calls
     def send_survey_query_to_vns(self, sq: SurveyQuery):
         """SendSurveyQueryToVNs (api_skipchain.go:16): announce the survey to the
@@ -227,7 +300,8 @@ class DrynxClient:
 
 
 def serve_iterative_extreme(node) -> list:
-    """A rank without the querier serves one iterative min/max search: one
+    """A rank without the querier serves one iterative search (min/max digits or
+    the count rounds of a quantile): one
     ``run_survey(None)`` per round, the number of rounds derived from the
     first round's query.  Returns the rounds' SurveyResults."""
     res = node.run_survey(None)
@@ -237,6 +311,9 @@ def serve_iterative_extreme(node) -> list:
     op = sq.Query.Operation
     L = iter_rounds(op.QueryMin, op.QueryMax, sq.IterBase)
     return [res] + [node.run_survey(None) for _ in range(L - 1)]
+
+
+serve_iterative = serve_iterative_extreme
 
 
 def lr_parameters(**kw) -> LogisticRegressionParameters:

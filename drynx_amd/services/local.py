@@ -80,16 +80,25 @@ def make_survey(client: DrynxClient, cluster, op_name: str, *, query_min=0, quer
 
 def make_iterative_survey(client: DrynxClient, cluster, op_name: str, base: int, *, query_min=0, query_max=10,
                           rows=10, group_by=(1,), proofs=0, thresholds=None, survey_id=None, sig_device="cpu",
-                          deterministic_sigs=False, verification_sharding=0, with_vns=None, range_proof_mode=0):
+                          deterministic_sigs=False, verification_sharding=0, with_vns=None, range_proof_mode=0,
+                          ranges=None):
     """The survey ``DrynxClient.send_iterative_extreme(sq, base)`` runs in rounds:
     a ``min``/``max`` over the full domain [query_min, query_max] whose ranges
     and input-validation signatures cover the ``base`` outputs of a round
     ((2, 1) each, made once and shared by every round) instead of one per
-    value of the domain."""
+    value of the domain.  For ``frequencyCount`` it is the survey
+    ``send_iterative_quantile`` runs: the outputs are counts, and with proofs
+    the ``ranges`` given ((u, l), or one per output) serve all ``base`` columns."""
     from ..query import iter_operation
 
+    if op_name == "frequencyCount":
+        if proofs and ranges is None:
+            raise ValueError("an iterative frequencyCount with proofs needs the ranges of its counts")
+        ranges = ranges if proofs else None
+    else:
+        ranges = [2, 1] if proofs else None
     sq = make_survey(client, cluster, op_name, query_min=query_min, query_max=query_min + base - 1, rows=rows,
-                     group_by=group_by, proofs=proofs, ranges=[2, 1] if proofs else None, thresholds=thresholds,
+                     group_by=group_by, proofs=proofs, ranges=ranges, thresholds=thresholds,
                      survey_id=survey_id, sig_device=sig_device, deterministic_sigs=deterministic_sigs,
                      verification_sharding=verification_sharding, with_vns=with_vns, range_proof_mode=range_proof_mode)
     sq.Query.Operation = iter_operation(op_name, query_min, query_max, base)

@@ -22,7 +22,7 @@ import tempfile
 from ..parallel.comm import init_distributed, make_comm
 from ..parallel.netem import flow_hops
 from ..query import QueryDiffP, LogisticRegressionParameters
-from ..services.api import DrynxClient, serve_iterative_extreme
+from ..services.api import DrynxClient, serve_iterative
 from ..services.local import local_cluster, make_iterative_survey, make_survey
 from ..utils import timers
 from ..utils.log import get_logger
@@ -116,7 +116,7 @@ def run_row(glob: dict, row: dict, comm, device, workdir, netem: str = "sleep"):
                            Scale=float(row.get("DiffPScale", 1)), Limit=float(row.get("DiffPLimit", 1)))
     results = []
     client = DrynxClient(node, device=device) if comm.rank == 0 else None
-    iter_base = int(row.get("IterBase", 0))  # optional column (extension): iterative min/max in this base
+    iter_base = int(row.get("IterBase", 0))  # optional column (extension): iterative min/max/quantile in this base
     for rnd in range(int(glob.get("Rounds", 1))):
         t = timers.start_timer("Simulation")
         if iter_base:
@@ -165,22 +165,31 @@ def run_row(glob: dict, row: dict, comm, device, workdir, netem: str = "sleep"):
 
 
 def _run_iterative(row, glob, base, cl, node, client, comm, device, per, proofs):
-    """One iterative min/max search of a runfile row with an ``IterBase`` column
-    (every round a query of its own); returns [value] on rank 0."""
+    """One iterative search of a runfile row with an ``IterBase`` column (every
+    round a query of its own): min/max, or for ``frequencyCount`` the quantile
+    of the optional ``IterQuantile`` column ("num/den", default "1/2");
+    returns [value] on rank 0."""
     if comm.rank != 0:
-        serve_iterative_extreme(node)
+        serve_iterative(node)
         return None
     thr_g, thr_o = float(row.get("ThresholdGeneral", 0)), float(row.get("ThresholdOther", 0))
-    sq = make_iterative_survey(client, cl, str(row["OperationName"]), base, query_min=int(row.get("MinData", 0)),
+    op_name = str(row["OperationName"])
+    hist = op_name == "frequencyCount"
+    rg = ranges_for(int(row.get("Ranges", -1)), base) if hist and proofs else None
+    sq = make_iterative_survey(client, cl, op_name, base, query_min=int(row.get("MinData", 0)),
                                query_max=int(row.get("MaxData", 1)), rows=int(row.get("DPRows", 1)),
-                               group_by=glob.get("GroupByValues", [1]), proofs=proofs,
+                               group_by=glob.get("GroupByValues", [1]), proofs=proofs, ranges=rg,
                                thresholds=[thr_g, thr_o, thr_o, 0.0, thr_o] if proofs else None, sig_device=device)
     ids = [p.identity() for p in cl.dps]
     n_cn = len(cl.cns)
     sq.ServerToDP = {c.id: ids[i * per:(i + 1) * per] for i, c in enumerate(cl.cns)}
     if ids[n_cn * per:]:
         sq.ServerToDP[cl.cns[0].id] += ids[n_cn * per:]
-    value, _ = client.send_iterative_extreme(sq, base)
+    if hist:
+        num, _, den = str(row.get("IterQuantile", "1/2")).partition("/")
+        value, _ = client.send_iterative_quantile(sq, base, int(num), int(den or 1))
+    else:
+        value, _ = client.send_iterative_extreme(sq, base)
     return [value]
 
 
