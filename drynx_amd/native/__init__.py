@@ -23,6 +23,8 @@ import numpy as np
 
 import torch
 
+from .. import rounds
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # DRYNX_NATIVE_LIB selects another build of the library (e.g. the host-sanitizer
 # build, build/libdrynx_native_asan.so); default: the in-tree gfx950 build
@@ -140,8 +142,7 @@ _SIGS = {
     "dx_fold_steps": [],
     "dx_rp_coeffs": [_P, _P, _P, _L],
     "dx_int_moments": [_I, _P, _P, _L, _I, _P, _L, _P, _I, _P, _P],
-    "dx_extreme_digit_bits": [_I, _P, _P, _L, _P, _L, _P, _L, _I, _L, _L, _L, _L, _L, _L, _P, _P],
-    "dx_digit_histogram": [_I, _P, _P, _L, _P, _L, _P, _L, _L, _L, _L, _L, _L, _L, _P, _P],
+    "dx_iter_round": [_I, _P, _P, _L, _P, _L, _P, _L, _I, _L, _L, _L, _L, _L, _P, _P],
     "dx_sha256_rows": [_I, _P, _P, _L, _L, _L, _L, _P],
     "dx_sha256_segments": [_I, _P, _P, _L, _L, _L, _P],
     "dx_g1_aff_to_uv": [_I, _P, _P, _L],
@@ -1164,106 +1165,55 @@ def int_moments(Z: torch.Tensor, seg_rows, pairs) -> torch.Tensor:
     return out
 
 
-EXTREME_MAX_BASE = 65536
-EXTREME_MAX_RANGE = 1 << 40
+_ITER_KINDS = {"min": 0, "max": 1, "frequencyCount": 2}
 
 
-def extreme_digit_bits(Z: torch.Tensor, seg_rows, is_max: bool, qmin: int, qmax: int, base: int, round: int,
-                       prefix: int) -> torch.Tensor:
-    """K14b (csrc/kernels/dx_extreme.hip): the [G, base] int64 rows every DP of a
-    batch encrypts in round ``round`` of the iterative min/max query.
-
-    Z [rows, n_in] holds the DPs' records back to back (``seg_rows[g]`` rows for
-    DP g; only column 0 is read, through Z's row stride).  With R = qmax - qmin
-    + 1 and L the smallest integer with base^L >= R, DP g's clamped extreme e
-    gives o = e - qmin; if o div base^(L-round) == prefix its value v is the
-    digit (o div base^(L-1-round)) mod base, otherwise (and for a DP without
-    records) v is neutral: 0 for max, base for min.  Row g is the unary encoding
-    of v over [0, base-1]: [i < v] for max, [i >= v] for min.  Two launches for
-    all DPs (tile partials, then the rows); the tile plan is int_moments'."""
-    assert Z.dtype == torch.int64 and Z.dim() == 2
-    qmin, qmax, base, k, prefix = int(qmin), int(qmax), int(base), int(round), int(prefix)
-    R = qmax - qmin + 1
-    if not 2 <= base <= EXTREME_MAX_BASE or not 1 <= R <= EXTREME_MAX_RANGE:
-        raise ValueError(f"extreme_digit_bits: base {base}, {R} values")
-    L, p = 1, base
-    while p < R:
-        p *= base
-        L += 1
-    if not 0 <= k < L or not 0 <= prefix < base ** k:
-        raise ValueError(f"extreme_digit_bits: round {k} of {L}, prefix {prefix}")
-    counts = np.asarray(seg_rows, dtype=np.int64).reshape(-1)
-    G = len(counts)
-    if counts.sum() != Z.shape[0] or (G and counts.min() < 0):
-        raise ValueError(f"extreme_digit_bits: segments cover {counts.sum()} rows, Z has {Z.shape[0]}")
-    if Z.shape[0] and Z.shape[1] < 1:
-        raise ValueError("extreme_digit_bits: Z has no column")
-    out = torch.empty((G, base), dtype=torch.int64, device=Z.device)
-    if G == 0:
-        return out
-    plan, first = _tile_plan(counts)
-    n_tiles = len(plan)
-    # one upload: the tiles, then every DP's tile range
-    desc = _upload(np.concatenate([plan.reshape(-1), first]), Z.device)
-    partial = torch.empty((max(1, n_tiles),), dtype=torch.int64, device=Z.device)
-    g, s = _ctx(out)
-    # (Z is read in place: a view's row stride is the kernel's ldz)
-    _call("dx_extreme_digit_bits", g, s, _ptr(Z, strided=True), Z.stride(0) if Z.shape[0] > 1 else 1,
-          _ptr(desc[: 3 * n_tiles]), n_tiles, _ptr(desc[3 * n_tiles:]), G, 1 if is_max else 0, qmin, qmax, base,
-          base ** (L - k), base ** (L - 1 - k), prefix, _ptr(partial), _ptr(out))
-    return out
-
-
-DIGIT_HIST_MAX_BASE = 4096
-DIGIT_HIST_MAX_RANGE = 1 << 40
-
-
-def digit_histogram(Z: torch.Tensor, seg_rows, qmin: int, qmax: int, base: int, round: int,
-                    prefix: int) -> torch.Tensor:
-    """K14c (csrc/kernels/dx_digit_hist.hip): the [G, base] int64 counts every DP
-    of a batch encrypts in round ``round`` of the iterative frequencyCount (the
-    rounds of a quantile search).
+def iter_round(name: str, Z: torch.Tensor, seg_rows, qmin: int, qmax: int, base: int, round: int,
+               prefix: int) -> torch.Tensor:
+    """K14b / K14c (csrc/kernels/dx_iter_round.hip): the [G, base] int64 rows
+    every DP of a batch encrypts in round ``round`` of the iterative ``name``
+    query (``min``, ``max`` or ``frequencyCount``, the rounds of a quantile
+    search).
 
     Z [rows, n_in] holds the DPs' records back to back (``seg_rows[g]`` rows for
     DP g; only column 0 is read, through Z's row stride).  With R = qmax - qmin
-    + 1 and L the smallest integer with base^L >= R, a record x of DP g inside
-    [qmin, qmax] has o = x - qmin and counts in bin (o div base^(L-1-round)) mod
-    base iff o div base^(L-round) == prefix; records outside the domain are
-    dropped.  Two launches for all DPs (per-tile LDS histograms, then the sum
-    over each DP's tiles); the tile plan is int_moments' with tiles of at least
-    ``base`` rows."""
+    + 1 and L the smallest integer with base^L >= R, an offset o = x - qmin
+    lies under the prefix iff o div base^(L-round) == prefix, and its digit is
+    (o div base^(L-1-round)) mod base (``rounds.iter_round``).  min / max: DP
+    g's clamped extreme gives o; under the prefix its value v is that digit,
+    otherwise (and for a DP without records) v is neutral: 0 for max, base for
+    min.  Row g is the unary encoding of v over [0, base-1]: [i < v] for max,
+    [i >= v] for min.  frequencyCount: row g counts DP g's records inside
+    [qmin, qmax] under the prefix by digit; records outside the domain are
+    dropped.  Two launches for all DPs (tile partials -- extremes, or LDS
+    histograms -- then the rows); the tile plan is int_moments', for counts
+    with tiles of at least ``base`` rows."""
     assert Z.dtype == torch.int64 and Z.dim() == 2
-    qmin, qmax, base, k, prefix = int(qmin), int(qmax), int(base), int(round), int(prefix)
-    R = qmax - qmin + 1
-    if not 2 <= base <= DIGIT_HIST_MAX_BASE or not 1 <= R <= DIGIT_HIST_MAX_RANGE:
-        raise ValueError(f"digit_histogram: base {base}, {R} values")
-    L, p = 1, base
-    while p < R:
-        p *= base
-        L += 1
-    if not 0 <= k < L or not 0 <= prefix < base ** k:
-        raise ValueError(f"digit_histogram: round {k} of {L}, prefix {prefix}")
+    qmin, qmax, base, prefix = int(qmin), int(qmax), int(base), int(prefix)
+    _, lo = rounds.iter_round(name, qmin, qmax, base, round, prefix)
+    counting = name == "frequencyCount"
     counts = np.asarray(seg_rows, dtype=np.int64).reshape(-1)
     G = len(counts)
     if counts.sum() != Z.shape[0] or (G and counts.min() < 0):
-        raise ValueError(f"digit_histogram: segments cover {counts.sum()} rows, Z has {Z.shape[0]}")
+        raise ValueError(f"iterative {name}: segments cover {counts.sum()} rows, Z has {Z.shape[0]}")
     if Z.shape[0] and Z.shape[1] < 1:
-        raise ValueError("digit_histogram: Z has no column")
+        raise ValueError(f"iterative {name}: Z has no column")
     out = torch.empty((G, base), dtype=torch.int64, device=Z.device)
     if G == 0:
         return out
-    plan, first = _tile_plan(counts, base)
+    plan, first = _tile_plan(counts, base) if counting else _tile_plan(counts)
     n_tiles = len(plan)
-    if n_tiles and int((plan[:, 2] - plan[:, 1]).max()) >= 1 << 31:
-        raise ValueError("digit_histogram: a tile of 2^31 rows or more")
+    if counting and n_tiles and int((plan[:, 2] - plan[:, 1]).max()) >= 1 << 31:
+        raise ValueError(f"iterative {name}: a tile of 2^31 rows or more")
     # one upload: the tiles, then every DP's tile range
     desc = _upload(np.concatenate([plan.reshape(-1), first]), Z.device)
-    partial = torch.empty((max(1, n_tiles), base), dtype=torch.int64, device=Z.device)
+    partial = torch.empty((max(1, n_tiles), base) if counting else (max(1, n_tiles),), dtype=torch.int64,
+                          device=Z.device)
     g, s = _ctx(out)
     # (Z is read in place: a view's row stride is the kernel's ldz)
-    _call("dx_digit_histogram", g, s, _ptr(Z, strided=True), Z.stride(0) if Z.shape[0] > 1 else 1,
-          _ptr(desc[: 3 * n_tiles]), n_tiles, _ptr(desc[3 * n_tiles:]), G, qmin, qmax, base, base ** (L - k),
-          base ** (L - 1 - k), prefix, _ptr(partial), _ptr(out))
+    _call("dx_iter_round", g, s, _ptr(Z, strided=True), Z.stride(0) if Z.shape[0] > 1 else 1,
+          _ptr(desc[: 3 * n_tiles]), n_tiles, _ptr(desc[3 * n_tiles:]), G, _ITER_KINDS[name], qmin, qmax, base, lo,
+          prefix, _ptr(partial), _ptr(out))
     return out
 
 

@@ -23,7 +23,7 @@ import torch
 
 from ..crypto import bn254 as bn
 from ..crypto import elgamal as eg
-from ..query import Operation
+from ..query import ITER_OPERATIONS, Operation
 
 
 @dataclass
@@ -220,73 +220,37 @@ def batch_values(name: str, Z: torch.Tensor, seg_rows, qmin: int = 0, qmax: int 
     raise ValueError(f"{name} has no batched encoder")
 
 
-def extreme_digit_values(operation: Operation, Z: torch.Tensor, seg_rows, base: int, rnd: int,
-                         prefix: int) -> torch.Tensor:
-    """[n_dp, base] int64 values of one round of the iterative min/max
-    (``SurveyQuery.IterBase``): per DP the 0/1 values the unary encoders above
-    emit for its round value over the domain [0, base-1] -- the base-``base``
-    digit ``rnd`` of its clamped extreme if the leading digits equal
-    ``prefix``, the neutral value otherwise.  Two launches for every DP of the
-    batch and no torch op in between (``native.extreme_digit_bits``); the host
-    path runs the same entry."""
-    from .. import native as nt
-
-    if operation.NameOp not in ("min", "max"):
-        raise ValueError(f"{operation.NameOp} has no iterative rounds")
-    return nt.extreme_digit_bits(Z, seg_rows, operation.NameOp == "max", operation.QueryMin, operation.QueryMax,
-                                 base, rnd, prefix)
-
-
-def encode_extreme_digit(data, operation: Operation, base: int, rnd: int, prefix: int, pk, with_proofs=False,
-                         ranges=None):
-    """One DP's response to a round of the iterative min/max: the values of
-    ``extreme_digit_values`` for its records, OR-encoded (min) or AND-encoded
-    (max) as ``encode_min`` / ``encode_max`` encode theirs."""
-    x = _t(data[0], pk.device).reshape(-1).to(torch.int64)
-    vals = extreme_digit_values(operation, x[:, None], [x.numel()], base, rnd, prefix)[0].cpu().tolist()
-    if operation.NameOp == "min":
-        return encode_bits([v != 0 for v in vals], pk, "or", with_proofs, ranges)
-    return encode_bits([v == 0 for v in vals], pk, "and", with_proofs, ranges)  # values are the inverted AND bits
-
-
-def digit_histogram_values(operation: Operation, Z: torch.Tensor, seg_rows, base: int, rnd: int,
-                           prefix: int) -> torch.Tensor:
-    """[n_dp, base] int64 counts of one round of the iterative frequencyCount
-    (the rounds of a quantile search): per DP the histogram of the
-    base-``base`` digit ``rnd`` of its in-domain records whose leading digits
-    equal ``prefix``; records outside the domain are dropped as the one-shot
-    histogram drops them.  Two launches for every DP of the batch
-    (``native.digit_histogram``); the host path runs the same entry."""
-    from .. import native as nt
-
-    if operation.NameOp != "frequencyCount":
-        raise ValueError(f"{operation.NameOp} has no digit histogram")
-    return nt.digit_histogram(Z, seg_rows, operation.QueryMin, operation.QueryMax, base, rnd, prefix)
-
-
-def encode_digit_histogram(data, operation: Operation, base: int, rnd: int, prefix: int, pk, with_proofs=False,
-                           ranges=None):
-    """One DP's response to a round of the iterative frequencyCount: the counts
-    of ``digit_histogram_values`` for its records, encrypted as integers like
-    ``encode_frequency_count``'s."""
-    x = _t(data[0], pk.device).reshape(-1).to(torch.int64)
-    vals = digit_histogram_values(operation, x[:, None], [x.numel()], base, rnd, prefix)[0].cpu().tolist()
-    return _encrypt_with_proofs(pk, vals, with_proofs, ranges)
-
-
 def iterative_values(operation: Operation, Z: torch.Tensor, seg_rows, base: int, rnd: int, prefix: int):
-    """The values of one round of an iterative query, by operation."""
-    if operation.NameOp == "frequencyCount":
-        return digit_histogram_values(operation, Z, seg_rows, base, rnd, prefix)
-    return extreme_digit_values(operation, Z, seg_rows, base, rnd, prefix)
+    """[n_dp, base] int64 values of one round of an iterative query
+    (``SurveyQuery.IterBase``), by operation.  min / max: per DP the 0/1 values
+    the unary encoders above emit for its round value over the domain [0,
+    base-1] -- the base-``base`` digit ``rnd`` of its clamped extreme if the
+    leading digits equal ``prefix``, the neutral value otherwise.
+    frequencyCount (the rounds of a quantile search): per DP the histogram of
+    that digit among its in-domain records whose leading digits equal
+    ``prefix``; records outside the domain are dropped as the one-shot
+    histogram drops them.  Two launches for every DP of the batch and no torch
+    op in between (``native.iter_round``); the host path runs the same entry."""
+    from .. import native as nt
+
+    if operation.NameOp not in ITER_OPERATIONS:
+        raise ValueError(f"{operation.NameOp} has no iterative rounds")
+    return nt.iter_round(operation.NameOp, Z, seg_rows, operation.QueryMin, operation.QueryMax, base, rnd, prefix)
 
 
 def encode_iterative(data, operation: Operation, base: int, rnd: int, prefix: int, pk, with_proofs=False,
                      ranges=None):
-    """One DP's response to one round of an iterative query, by operation."""
+    """One DP's response to one round of an iterative query: the values of
+    ``iterative_values`` for its records, encrypted as integers like
+    ``encode_frequency_count``'s (frequencyCount), OR-encoded (min) or
+    AND-encoded (max) as ``encode_min`` / ``encode_max`` encode theirs."""
+    x = _t(data[0], pk.device).reshape(-1).to(torch.int64)
+    vals = iterative_values(operation, x[:, None], [x.numel()], base, rnd, prefix)[0].cpu().tolist()
     if operation.NameOp == "frequencyCount":
-        return encode_digit_histogram(data, operation, base, rnd, prefix, pk, with_proofs, ranges)
-    return encode_extreme_digit(data, operation, base, rnd, prefix, pk, with_proofs, ranges)
+        return _encrypt_with_proofs(pk, vals, with_proofs, ranges)
+    if operation.NameOp == "min":
+        return encode_bits([v != 0 for v in vals], pk, "or", with_proofs, ranges)
+    return encode_bits([v == 0 for v in vals], pk, "and", with_proofs, ranges)  # values are the inverted AND bits
 
 
 def encrypt_batch(pk: eg.PublicKeyTable, values: torch.Tensor, bits: bool):

@@ -18,6 +18,7 @@ from dataclasses import dataclass, field, fields, is_dataclass
 from typing import Optional
 
 from .crypto import oracle as O
+from .rounds import ITER_MAX_BASE, ITER_MAX_HIST_BASE, ITER_MAX_RANGE, ITER_OPERATIONS, iter_rounds  # re-exported
 from .utils.log import get_logger
 
 log = get_logger("query")
@@ -193,12 +194,12 @@ class SurveyQuery:
     # a digit-by-digit search: the DPs answer with the unary encoding (b
     # outputs) of the IterRound-th base-b digit of their extreme, most
     # significant first, if its leading digits equal IterPrefix, and with the
-    # neutral value otherwise (csrc/kernels/dx_extreme.hip).  IterSurveyID is
+    # neutral value otherwise (csrc/kernels/dx_iter_round.hip).  IterSurveyID is
     # the id the rounds of one search share: generated records are seeded from
     # it, so every round sees the same data.  0 = the reference's one-shot query.
     # A frequencyCount round (the rounds of a quantile search) answers with the
     # b counts of that digit among the DP's in-domain records under the prefix
-    # (csrc/kernels/dx_digit_hist.hip).
+    # (the same kernel file).
     IterBase: int = 0
     IterRound: int = 0
     IterPrefix: int = 0
@@ -389,26 +390,6 @@ def check_parameters(sq: SurveyQuery, diffp: bool) -> bool:
     for m in msg:
         log.warning(m)
     return not msg
-
-
-ITER_MAX_BASE = 65536
-ITER_MAX_HIST_BASE = 4096  # frequencyCount rounds: one LDS counter per output (csrc/kernels/dx_digit_hist.hip)
-ITER_MAX_RANGE = 1 << 40  # every power of the base a round divides by stays far inside int64
-ITER_OPERATIONS = ("min", "max", "frequencyCount")
-
-
-def iter_rounds(qmin: int, qmax: int, base: int) -> int:
-    """Rounds L of the iterative min/max over [qmin, qmax] in base ``base``: the
-    smallest integer with base^L >= qmax - qmin + 1 (integer products, no log)."""
-    R = int(qmax) - int(qmin) + 1
-    base = int(base)
-    if base < 2 or R < 1:
-        raise ValueError(f"no iterative rounds for base {base} over {R} values")
-    L, p = 1, base
-    while p < R:
-        p *= base
-        L += 1
-    return L
 
 
 def _check_iterative(sq: SurveyQuery) -> list:

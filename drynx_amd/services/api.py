@@ -140,6 +140,39 @@ class DrynxClient:
         memo[(id(cols), base)] = (cols, cut)
         return cut
 
+    def _iterative_walk(self, sq: SurveyQuery, base: int, what: str, decoder, rule, on_round):
+        """The rounds of one iterative search over ``sq``: round k's query carries
+        the k digits found so far, ``decoder`` turns its aggregate into
+        ``client_out`` (one entry per group) and ``rule(k, prefix, client_out)``
+        into ``(digit, failed, empty)``: the round's digit, a message when the
+        answers contradict an earlier round or each other, or that there is
+        nothing to search.  Returns ``(prefix, empty, rounds, iter_id)``;
+        raises the first failure."""
+        op = sq.Query.Operation
+        L = iter_rounds(op.QueryMin, op.QueryMax, base)
+        iter_id = sq.SurveyID or new_survey_id()
+        collective = getattr(getattr(self.entry, "comm", None), "world", 1) > 1
+        # With several ranks the others serve exactly L rounds (``serve_iterative``):
+        # a search that has failed, or found nothing to search, still runs them all.
+        prefix, rounds, failed, empty = 0, [], None, False
+        for k in range(L):
+            rq = self.iterative_round_query(sq, base, k, prefix, iter_id)
+            if k == 0 and not check_parameters(rq, False):
+                raise ValueError("the iterative query fails CheckParameters")
+            res = self.entry.run_survey(rq, on_result=decoder)
+            rounds.append(res)
+            digit = 0
+            if failed is None and not empty:
+                digit, failed, empty = rule(k, prefix, res.client_out)
+            if (failed is not None or empty) and not collective:
+                break
+            if on_round is not None:
+                on_round(k, digit, res)
+            prefix = prefix * base + digit
+        if failed is not None:
+            raise RuntimeError(f"iterative {what} {iter_id}: {failed}")
+        return prefix, empty, rounds, iter_id
+
     def send_iterative_extreme(self, sq: SurveyQuery, base: int, on_round=None):
         """Iterative min/max (extension): the result of the ``min``/``max`` survey
         ``sq`` found one base-``base`` digit per round, most significant first,
@@ -151,10 +184,7 @@ class DrynxClient:
         after each round.  Raises when the DPs' answers contradict an earlier
         round (a ``min`` round nobody matches) or the groups disagree."""
         op = sq.Query.Operation
-        L = iter_rounds(op.QueryMin, op.QueryMax, base)
         is_max = op.NameOp == "max"
-        iter_id = sq.SurveyID or new_survey_id()
-        collective = getattr(getattr(self.entry, "comm", None), "world", 1) > 1
 
         def digits(partial):
             """Per group the first zero (max) / non-zero (min) aggregate of the round, None without one."""
@@ -165,34 +195,18 @@ class DrynxClient:
                     out.append(next((i for i, b in enumerate(nz) if (b == 0) == is_max), None))
             return out
 
-        # With several ranks the others serve exactly L rounds (``serve_iterative_extreme``):
-        # a search that has failed, or found that no DP has records, still runs them all.
-        prefix, rounds, failed, empty = 0, [], None, False
-        for k in range(L):
-            rq = self.iterative_round_query(sq, base, k, prefix, iter_id)
-            if k == 0 and not check_parameters(rq, False):
-                raise ValueError("the iterative query fails CheckParameters")
-            res = self.entry.run_survey(rq, on_result=digits)
-            rounds.append(res)
-            ds = res.client_out
-            digit = ds[0]
-            if failed is None and not empty:
-                if any(d != digit for d in ds):
-                    failed = f"round {k}: the groups disagree on the digit ({ds})"
-                elif digit is None and is_max:
-                    failed = f"round {k}: no zero aggregate (the last output of a max round is always zero)"
-                elif digit is None and k > 0:
-                    failed = f"round {k}: no DP matches the prefix {prefix}: an answer changed between rounds"
-                elif digit is None:
-                    empty = True  # min, round 0: no DP has records -> QueryMin, as the one-shot decode returns
-            if (failed is not None or empty) and not collective:
-                break
-            digit = digit or 0
-            if on_round is not None:
-                on_round(k, digit, res)
-            prefix = prefix * base + digit
-        if failed is not None:
-            raise RuntimeError(f"iterative {op.NameOp} {iter_id}: {failed}")
+        def rule(k, prefix, ds):
+            digit, failed = ds[0], None
+            if any(d != digit for d in ds):
+                failed = f"round {k}: the groups disagree on the digit ({ds})"
+            elif digit is None and is_max:
+                failed = f"round {k}: no zero aggregate (the last output of a max round is always zero)"
+            elif digit is None and k > 0:
+                failed = f"round {k}: no DP matches the prefix {prefix}: an answer changed between rounds"
+            # min, round 0, no digit: no DP has records -> QueryMin, as the one-shot decode returns
+            return digit or 0, failed, digit is None and failed is None
+
+        prefix, empty, rounds, _ = self._iterative_walk(sq, base, op.NameOp, digits, rule, on_round)
         return float(op.QueryMin + (0 if empty else prefix)), rounds
 
     # ------------------------------------------------------------------ iterative quantiles
@@ -217,9 +231,6 @@ class DrynxClient:
         op = sq.Query.Operation
         if op.NameOp != "frequencyCount":
             raise ValueError(f"an iterative quantile runs on a frequencyCount survey, not {op.NameOp}")
-        L = iter_rounds(op.QueryMin, op.QueryMax, base)
-        iter_id = sq.SurveyID or new_survey_id()
-        collective = getattr(getattr(self.entry, "comm", None), "world", 1) > 1
         round_op = iter_operation(op.NameOp, op.QueryMin, op.QueryMax, base)
 
         def counts(partial):
@@ -227,43 +238,31 @@ class DrynxClient:
             with timers.timed("Decode"):
                 return [[int(round(v)) for v in self.decode(cv.to(self.device), round_op)] for cv in partial.groups()]
 
-        # With several ranks the others serve exactly L rounds (``serve_iterative``):
-        # a search that has failed, or found no record, still runs them all.
-        prefix, rounds, failed, empty, t, chosen = 0, [], None, False, 0, 0
-        for k in range(L):
-            rq = self.iterative_round_query(sq, base, k, prefix, iter_id)
-            if k == 0 and not check_parameters(rq, False):
-                raise ValueError("the iterative query fails CheckParameters")
-            res = self.entry.run_survey(rq, on_result=counts)
-            rounds.append(res)
-            cs = res.client_out
-            c, digit = cs[0], 0
-            if failed is None and not empty:
-                total = sum(c)
-                if any(x != c for x in cs):
-                    failed = f"round {k}: the groups disagree on the counts"
-                elif k == 0 and total == 0:
-                    empty = True
-                elif k == 0:
-                    t = max(1, (num * total + den - 1) // den)
-                elif total != chosen:
-                    failed = (f"round {k}: {total} records under the prefix {prefix}, round {k - 1} counted "
-                              f"{chosen}: an answer changed between rounds")
-            if (failed is not None or empty) and not collective:
-                break
-            if failed is None and not empty:
-                below = 0
-                for digit, x in enumerate(c):  # the smallest digit whose cumulative count reaches t
-                    if below + x >= t:
-                        break
-                    below += x
-                t -= below
-                chosen = c[digit]
-            if on_round is not None:
-                on_round(k, digit, res)
-            prefix = prefix * base + digit
-        if failed is not None:
-            raise RuntimeError(f"iterative quantile {iter_id}: {failed}")
+        t, chosen = 0, 0  # the rank still to walk, the count of the bin chosen in the round before
+
+        def rule(k, prefix, cs):
+            nonlocal t, chosen
+            c = cs[0]
+            total = sum(c)
+            if any(x != c for x in cs):
+                return 0, f"round {k}: the groups disagree on the counts", False
+            if k == 0 and total == 0:
+                return 0, None, True
+            if k == 0:
+                t = max(1, (num * total + den - 1) // den)
+            elif total != chosen:
+                return 0, (f"round {k}: {total} records under the prefix {prefix}, round {k - 1} counted "
+                           f"{chosen}: an answer changed between rounds"), False
+            below = 0
+            for digit, x in enumerate(c):  # the smallest digit whose cumulative count reaches t
+                if below + x >= t:
+                    break
+                below += x
+            t -= below
+            chosen = c[digit]
+            return digit, None, False
+
+        prefix, empty, rounds, iter_id = self._iterative_walk(sq, base, "quantile", counts, rule, on_round)
         if empty:
             raise RuntimeError(f"iterative quantile {iter_id}: no records in the domain")
         return float(op.QueryMin + prefix), rounds
@@ -299,7 +298,7 @@ class DrynxClient:
         return self.entry.close_db(vn_id, remove)
 
 
-def serve_iterative_extreme(node) -> list:
+def serve_iterative(node) -> list:
     """A rank without the querier serves one iterative search (min/max digits or
     the count rounds of a quantile): one
     ``run_survey(None)`` per round, the number of rounds derived from the
@@ -311,9 +310,6 @@ def serve_iterative_extreme(node) -> list:
     op = sq.Query.Operation
     L = iter_rounds(op.QueryMin, op.QueryMax, sq.IterBase)
     return [res] + [node.run_survey(None) for _ in range(L - 1)]
-
-
-serve_iterative = serve_iterative_extreme
 
 
 def lr_parameters(**kw) -> LogisticRegressionParameters:

@@ -62,13 +62,14 @@ def records_for(seg_rows, qmin, qmax, seed, outside=True):
     full = [r for r in out if r]
     if not outside:
         return out
-    full[2][len(full[2]) // 2] = qmin - 3
-    full[3][-1] = qmax + 5
+    below, above = full[2 % len(full)], full[3 % len(full)]  # (with fewer than four DPs with records: two others)
+    below[len(below) // 2] = qmin - 3
+    above[-1] = qmax + 5
     return out
 
 
 def check_rows(device, seg_rows=SEG_ROWS, domains=DOMAINS):
-    """nt.extreme_digit_bits == the model, both modes, every round (prefix = the
+    """nt.iter_round == the model, both modes, every round (prefix = the
     model's global digits), one prefix nobody matches; Z has two columns."""
     host = []
     for n, (qmin, R, b) in enumerate(domains):
@@ -80,13 +81,14 @@ def check_rows(device, seg_rows=SEG_ROWS, domains=DOMAINS):
                          dtype=torch.int64).reshape(-1, 2).to(device)
         L = model_rounds(R, b)
         assert Q.iter_rounds(qmin, qmax, b) == L
-        for is_max in (True, False):
+        for name in ("max", "min"):
+            is_max = name == "max"
             digits = model_digits(dps, is_max, qmin, qmax, b)
             assert qmin + sum(d * b ** (L - 1 - k) for k, d in enumerate(digits)) == \
                 min(max((max if is_max else min)(flat), qmin), qmax)
             prefix = 0
             for k in range(L):
-                got = nt.extreme_digit_bits(Z, seg_rows, is_max, qmin, qmax, b, k, prefix)
+                got = nt.iter_round(name, Z, seg_rows, qmin, qmax, b, k, prefix)
                 assert got.dtype == torch.int64 and got.shape == (len(seg_rows), b) and got.device == Z.device
                 assert got.cpu().tolist() == [model_row(r, is_max, qmin, qmax, b, L, k, prefix) for r in dps]
                 host.append(got.cpu())
@@ -94,7 +96,7 @@ def check_rows(device, seg_rows=SEG_ROWS, domains=DOMAINS):
             if L > 1:  # a prefix no DP matches: every row neutral
                 os_ = {min(max((max if is_max else min)(r), qmin), qmax) - qmin for r in dps if r}
                 miss = next(p for p in range(b) if all(o // b ** (L - 1) != p for o in os_))
-                got = nt.extreme_digit_bits(Z, seg_rows, is_max, qmin, qmax, b, 1, miss).cpu().tolist()
+                got = nt.iter_round(name, Z, seg_rows, qmin, qmax, b, 1, miss).cpu().tolist()
                 assert got == [[0] * b for _ in seg_rows]  # [i < 0] and [i >= b] alike
                 assert got == [model_row(r, is_max, qmin, qmax, b, L, 1, miss) for r in dps]
     return host
@@ -104,6 +106,13 @@ def test_rows_equal_the_model():
     check_rows("cpu")
 
 
+WIDEST = dict(seg_rows=[0, 3, 70], domains=[(-5, 65537, 65536)])  # the cap of the min/max base: L = 2, 65536-wide rows
+
+
+def test_rows_at_the_widest_base():
+    assert len(check_rows("cpu", **WIDEST)) == 4
+
+
 def test_rows_argument_checks():
     Z = torch.zeros((3, 1), dtype=torch.int64)
     for bad in (dict(base=1), dict(base=65537), dict(rnd=3), dict(rnd=-1), dict(prefix=10, rnd=1),
@@ -111,8 +120,8 @@ def test_rows_argument_checks():
         a = dict(seg=[3], qmin=0, qmax=999, base=10, rnd=0, prefix=0)
         a.update(bad)
         with pytest.raises(ValueError):
-            nt.extreme_digit_bits(Z, a["seg"], True, a["qmin"], a["qmax"], a["base"], a["rnd"], a["prefix"])
-    assert nt.extreme_digit_bits(Z[:0], [], True, 0, 9, 10, 0, 0).shape == (0, 10)
+            nt.iter_round("max", Z, a["seg"], a["qmin"], a["qmax"], a["base"], a["rnd"], a["prefix"])
+    assert nt.iter_round("max", Z[:0], [], 0, 9, 10, 0, 0).shape == (0, 10)
 
 
 # ----------------------------------------------------------------------------- validation and carriers
@@ -373,8 +382,9 @@ def test_per_dp_encoder_matches_the_batch(env):
 # ----------------------------------------------------------------------------- two ranks, simulation
 def test_two_gloo_ranks_through_the_tool(tmp_path):
     env_ = dict(os.environ, OMP_NUM_THREADS="4", DX_NUM_THREADS="4")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "bench_max_iter.py"), "--gpus", "2", "--range",
-                        "1000", "--bases", "10", "--steps", "1", "--passes", "1", "--device", "cpu", "--no-classic",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "bench_iter.py"), "--query", "max", "--gpus", "2",
+                        "--range", "1000", "--bases", "10", "--steps", "1", "--passes", "1", "--device", "cpu",
+                        "--no-classic",
                         "--out-dir", str(tmp_path)], cwd=ROOT, env=env_, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     line = json.loads([x for x in r.stdout.splitlines() if x.startswith("{")][-1])

@@ -1,4 +1,4 @@
-"""Iterative min/max on the GPU: the K14b kernel pair (dx_extreme.hip) against
+"""Iterative min/max on the GPU: the K14b kernel pair (dx_iter_round.hip) against
 the pure-Python model and, bit for bit, against its host twin -- also with one
 DP of 200000 rows, where the tile plan's chunk is 128 rows -- and searches end
 to end at range 1000 in base 10 (three rounds), without and with proofs.  Run
@@ -20,6 +20,12 @@ def test_rows_equal_the_model_and_the_host(gpu_device):
     assert len(dev) == len(host) and all(torch.equal(a, b) for a, b in zip(dev, host))
 
 
+def test_rows_at_the_widest_base(gpu_device):
+    dev = ti.check_rows(gpu_device, **ti.WIDEST)
+    host = ti.check_rows("cpu", **ti.WIDEST)
+    assert len(dev) == len(host) == 4 and all(torch.equal(a, b) for a, b in zip(dev, host))
+
+
 def test_one_large_dp(gpu_device):
     """200000 + 0 + 70 rows: chunk = 128, 1563 tiles for DP 0 (stage 2 strides its partials)."""
     seg = [200_000, 0, 70]
@@ -30,16 +36,17 @@ def test_one_large_dp(gpu_device):
     g = torch.Generator().manual_seed(5)
     Z = torch.randint(qmin + 1000, qmax - 1000, (sum(seg), 1), generator=g)
     Zd = Z.to(gpu_device)
-    for is_max in (True, False):
+    for name in ("max", "min"):
+        is_max = name == "max"
         ext = [int(Z[:200_000].max() if is_max else Z[:200_000].min()), None,
                int(Z[200_000:].max() if is_max else Z[200_000:].min())]
         o = ext[0] - qmin
         for k in range(L):
             for prefix in {o // b ** (L - k), (ext[2] - qmin) // b ** (L - k)}:
-                got = nt.extreme_digit_bits(Zd, seg, is_max, qmin, qmax, b, k, prefix)
+                got = nt.iter_round(name, Zd, seg, qmin, qmax, b, k, prefix)
                 want = [ti.model_row([e] if e is not None else [], is_max, qmin, qmax, b, L, k, prefix) for e in ext]
                 assert got.cpu().tolist() == want
-                assert torch.equal(got.cpu(), nt.extreme_digit_bits(Z, seg, is_max, qmin, qmax, b, k, prefix))
+                assert torch.equal(got.cpu(), nt.iter_round(name, Z, seg, qmin, qmax, b, k, prefix))
 
 
 @pytest.fixture(scope="module")

@@ -16,6 +16,7 @@ import torch
 
 from drynx_amd import native as nt
 from drynx_amd import query as Q
+from drynx_amd import rounds
 from drynx_amd.ops import encoding as enc
 from drynx_amd.proofs import requests as prq
 from drynx_amd.services.api import DrynxClient
@@ -90,7 +91,7 @@ def records_for(seg_rows, qmin, qmax, b, seed):
 
 
 def check_rows(device, seg_rows=SEG_ROWS, domains=DOMAINS):
-    """nt.digit_histogram == the model in every round (prefix = the median
+    """nt.iter_round == the model in every round (prefix = the median
     walk's digits), one prefix nobody matches, the last round against the
     classic histogram, round 0 against the in-domain counts; Z has two columns."""
     rows = []
@@ -110,7 +111,7 @@ def check_rows(device, seg_rows=SEG_ROWS, domains=DOMAINS):
         assert classic.shape == (len(seg_rows), R)
         prefix = 0
         for k in range(L):
-            got = nt.digit_histogram(Z, seg_rows, qmin, qmax, b, k, prefix)
+            got = nt.iter_round("frequencyCount", Z, seg_rows, qmin, qmax, b, k, prefix)
             assert got.dtype == torch.int64 and got.shape == (len(seg_rows), b) and got.device == Z.device
             assert got.cpu().tolist() == [model_row(r, qmin, qmax, b, L, k, prefix) for r in dps]
             if k == 0:
@@ -120,7 +121,7 @@ def check_rows(device, seg_rows=SEG_ROWS, domains=DOMAINS):
                 prefix = prefix * b + digits[k]
         # the last round under the walk's prefix and under the last block of the domain (cut at R)
         for p in {prefix, (R - 1) // b}:
-            got = nt.digit_histogram(Z, seg_rows, qmin, qmax, b, L - 1, p).cpu()
+            got = nt.iter_round("frequencyCount", Z, seg_rows, qmin, qmax, b, L - 1, p).cpu()
             want = torch.zeros((len(seg_rows), b), dtype=torch.int64)
             cut = classic[:, p * b: p * b + b]
             want[:, : cut.shape[1]] = cut
@@ -129,7 +130,7 @@ def check_rows(device, seg_rows=SEG_ROWS, domains=DOMAINS):
         if L > 1:  # a prefix no record matches: every row zero
             seen = {(x - qmin) // b for x in flat if qmin <= x <= qmax}
             miss = next(p for p in range(b ** (L - 1)) if p not in seen)
-            got = nt.digit_histogram(Z, seg_rows, qmin, qmax, b, L - 1, miss).cpu().tolist()
+            got = nt.iter_round("frequencyCount", Z, seg_rows, qmin, qmax, b, L - 1, miss).cpu().tolist()
             assert got == [[0] * b for _ in seg_rows]
             assert got == [model_row(r, qmin, qmax, b, L, L - 1, miss) for r in dps]
     return rows
@@ -153,7 +154,7 @@ def check_large(device):
         digits = model_walk([recs], qmin, qmax, b, 1, 2)
         prefix = 0
         for k in range(L):
-            got = nt.digit_histogram(Z, [n], qmin, qmax, b, k, prefix).cpu()
+            got = nt.iter_round("frequencyCount", Z, [n], qmin, qmax, b, k, prefix).cpu()
             assert got.tolist() == [model_row(recs, qmin, qmax, b, L, k, prefix)] and int(got.sum()) > 0
             out.append(got)
             prefix = prefix * b + digits[k]
@@ -177,31 +178,41 @@ def test_rows_argument_checks():
         a = dict(seg=[3], qmin=0, qmax=999, base=10, rnd=0, prefix=0)
         a.update(bad)
         with pytest.raises(ValueError):
-            nt.digit_histogram(Z, a["seg"], a["qmin"], a["qmax"], a["base"], a["rnd"], a["prefix"])
-    assert nt.digit_histogram(Z[:0], [], 0, 9, 10, 0, 0).shape == (0, 10)
-    assert nt.digit_histogram(Z, [3], 0, (1 << 40) - 1, 4096, 3, 4096 ** 3 - 1).tolist() == [[0] * 4096]
-    assert (nt.DIGIT_HIST_MAX_BASE, nt.DIGIT_HIST_MAX_RANGE) == (4096, 1 << 40)
+            nt.iter_round("frequencyCount", Z, a["seg"], a["qmin"], a["qmax"], a["base"], a["rnd"], a["prefix"])
+    assert nt.iter_round("frequencyCount", Z[:0], [], 0, 9, 10, 0, 0).shape == (0, 10)
+    assert nt.iter_round("frequencyCount", Z, [3], 0, (1 << 40) - 1, 4096, 3, 4096 ** 3 - 1).tolist() == [[0] * 4096]
+    assert (rounds.ITER_MAX_HIST_BASE, rounds.ITER_MAX_RANGE) == (4096, 1 << 40)
 
 
 def test_entry_refuses_what_the_binding_refuses():
-    """The C entry's own checks (-2), called below the binding."""
+    """The C entry's own checks (-2), called below the binding: one rule for counts (kind 2), min (0) and max (1)."""
     Z = torch.zeros((3, 1), dtype=torch.int64)
     tiles = torch.tensor([0, 0, 3, 0, 1], dtype=torch.int64)  # one tile, then dp_first
-    part, out = torch.empty((1, 4096), dtype=torch.int64), torch.empty((1, 4096), dtype=torch.int64)
+    part, out = torch.empty((1, 8192), dtype=torch.int64), torch.empty((1, 8192), dtype=torch.int64)
 
-    def rc(qmin=0, qmax=999, base=10, hi=1000, lo=100, prefix=0, tl=tiles):
-        return nt._raw_call("dx_digit_histogram", 0, None, nt._ptr(Z), 1, nt._ptr(tl[:3]), 1, nt._ptr(tl[3:]), 1, qmin,
-                            qmax, base, hi, lo, prefix, nt._ptr(part), nt._ptr(out))
+    def rc(kind=2, qmin=0, qmax=999, base=10, lo=100, prefix=0, tl=tiles, G=1):
+        return nt._raw_call("dx_iter_round", 0, None, nt._ptr(Z), 1, nt._ptr(tl[:3]), 1, nt._ptr(tl[3:]), G, kind,
+                            qmin, qmax, base, lo, prefix, nt._ptr(part), nt._ptr(out))
 
     assert rc() == 0 and out[0, :10].tolist() == [3] + [0] * 9
-    assert rc(hi=10, lo=1, prefix=99) == 0
-    assert rc(base=1, hi=1, lo=1) == -2 and rc(base=4097, hi=4097, lo=1) == -2
+    assert rc(lo=1, prefix=99) == 0
+    assert rc(base=1, lo=1) == -2 and rc(base=4097, lo=1) == -2
     assert rc(qmax=1 << 40) == -2 and rc(qmax=-1) == -2
-    assert rc(hi=10000, lo=1000) == -2 and rc(hi=1, lo=0) == -2 and rc(hi=500, lo=50) == -2  # no round of the domain
-    assert rc(hi=1000, lo=10) == -2
-    assert rc(prefix=1) == -2 and rc(prefix=-1) == -2 and rc(hi=10, lo=1, prefix=100) == -2
+    assert rc(lo=1000) == -2 and rc(lo=0) == -2 and rc(lo=50) == -2  # no round of the domain
+    assert rc(prefix=1) == -2 and rc(prefix=-1) == -2 and rc(lo=1, prefix=100) == -2
     long = torch.tensor([0, 0, 1 << 31, 0, 1], dtype=torch.int64)
     assert rc(tl=long) == -2  # a tile of 2^31 rows: the 32-bit counters could wrap
+    for kind, row in ((0, [1] * 10), (1, [0] * 10)):  # three records 0: the digit 0 in unary, [i >= 0] and [i < 0]
+        assert rc(kind) == 0 and out[0, :10].tolist() == row
+        assert rc(kind, lo=1, prefix=99) == 0
+        assert rc(kind, base=1, lo=1) == -2 and rc(kind, base=65537, lo=1) == -2
+        assert rc(kind, qmax=1 << 40) == -2 and rc(kind, qmax=-1) == -2
+        assert rc(kind, lo=1000) == -2 and rc(kind, lo=0) == -2 and rc(kind, lo=50) == -2
+        assert rc(kind, prefix=1) == -2 and rc(kind, prefix=-1) == -2 and rc(kind, lo=1, prefix=100) == -2
+    assert rc(1, base=4097, lo=1) == 0 and out[0, :4097].tolist() == [0] * 4097  # the cap is the kind's
+    assert rc(3) == -2 and rc(-1) == -2
+    # the tile length limits the 32-bit counters only; checked before anything is read (no DP: no row is)
+    assert rc(2, tl=long, G=0) == -2 and rc(1, tl=long, G=0) == 0
 
 
 # ----------------------------------------------------------------------------- validation
@@ -421,8 +432,8 @@ def test_per_dp_encoder_matches_the_batch(env):
 # ----------------------------------------------------------------------------- two ranks, simulation
 def test_two_gloo_ranks_through_the_tool(tmp_path):
     env_ = dict(os.environ, OMP_NUM_THREADS="4", DX_NUM_THREADS="4")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "bench_quantile_iter.py"), "--gpus", "2",
-                        "--range", "1000", "--bases", "10", "--steps", "1", "--passes", "1", "--device", "cpu",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "bench_iter.py"), "--query", "quantile", "--gpus",
+                        "2", "--range", "1000", "--bases", "10", "--steps", "1", "--passes", "1", "--device", "cpu",
                         "--no-classic", "--out-dir", str(tmp_path)], cwd=ROOT, env=env_, capture_output=True,
                        text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]

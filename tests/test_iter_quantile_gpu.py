@@ -1,4 +1,4 @@
-"""Iterative quantiles on the GPU: the K14c kernel pair (dx_digit_hist.hip)
+"""Iterative quantiles on the GPU: the K14c kernel pair (dx_iter_round.hip)
 against the pure-Python model, the classic histogram and, bit for bit, its host
 twin -- also with one DP of 70000 rows at b = 1000 (68 tiles of 1024 rows and a
 ragged one; uniform records, then all in one bin) -- and rank walks end to end

@@ -1,23 +1,31 @@
-"""Iterative (digit-by-digit) quantile against the one-shot frequencyCount over a range of N values.
+"""Iterative (digit-by-digit) max or quantile against its one-shot query over a range of N values.
 
-3 CNs, 3 VNs and 10 DPs with ``--rows`` records each (default 100), uniform in
-[0, N), range proofs on every output with ranges sized to a DP's record count
-(u = 16, the smallest l with 16^l > rows), random per-CN per-column
-signatures, thresholds [1, 1, 1, 0, 1].  The ``--quantile`` (num/den, default
-1/2) is searched with ``DrynxClient.send_iterative_quantile`` once per base of
-``--bases`` and, where N <= 100000, the classic one-shot ``frequencyCount`` of
-the same domain is run and the quantile read off its histogram, alternating
-base / ... / classic / base / ... / classic (``--passes`` times, default 2) in
-one process on the same cluster and records.  Each run is a warm-up (which
-builds the run's prover and verifier tables: one signature set is resident at
-a time) plus ``--steps`` timed searches or queries.  Outside the timed region
-every round's block is checked (all proofs valid) and every result is compared
-with the clear nearest-rank quantile of all DPs' records.
+``--query max``: bench.py's ``--query max`` configuration (3 CNs, 3 VNs, 10 DPs
+with 100 records each, uniform in [0, N), (2, 1) range proofs on every output,
+random per-CN per-column signatures, thresholds [1, 1, 1, 0, 1]) is run as an
+iterative search (``DrynxClient.send_iterative_extreme``) and as the classic
+one-shot unary ``max``.
 
-On a GPU the encoder alone is timed too: the two-launch kernel pair
-(``native.digit_histogram``) on 10 DPs x 100000 records, uniform and with every
-record equal (all LDS atomics of a workgroup on one counter), device events
-after a warm-up.
+``--query quantile``: the same cluster with ``--rows`` records per DP (default
+100) and ranges sized to a DP's record count (u = 16, the smallest l with
+16^l > rows).  The ``--quantile`` (num/den, default 1/2) is searched with
+``DrynxClient.send_iterative_quantile``; the classic query is the one-shot
+``frequencyCount`` of the same domain, the quantile read off its histogram.
+
+The search runs once per base of ``--bases`` and, where N <= 100000, the
+classic query too, alternating base / ... / classic / base / ... / classic
+(``--passes`` times, default 2) in one process on the same cluster and
+records.  Each run is a warm-up (which builds the run's prover and verifier
+tables: one signature set is resident at a time) plus ``--steps`` timed
+searches or queries.  Outside the timed region every round's block is checked
+(all proofs valid) and every result is compared with the clear max, or the
+clear nearest-rank quantile, of all DPs' records.
+
+On a GPU the encoder alone is timed too, on 10 DPs x 100000 records with device
+events after a warm-up: the two-launch kernel pair (``native.iter_round``) for
+``max`` against ``ops.encoding.batch_values("max")`` at the same output width;
+for ``frequencyCount`` on uniform records and with every record equal (all LDS
+atomics of a workgroup on one counter).
 
 ``--gpus W`` (W > 1) starts W ranks; the ranks without the querier serve the
 rounds (``serve_iterative``).  Prints one JSON object; ``--out-dir`` also
@@ -40,28 +48,34 @@ import torch  # noqa: E402
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-import bench  # noqa: E402  (the launcher's argument forwarding and the world check, shared)
+import bench  # noqa: E402  (the max configuration, the reference rows, the launcher's argument forwarding, shared)
 from drynx_amd import native as nt  # noqa: E402
+from drynx_amd.ops import encoding as enc  # noqa: E402
 from drynx_amd.parallel.comm import init_distributed, make_comm  # noqa: E402
-from drynx_amd.query import ITER_MAX_HIST_BASE, iter_rounds, new_survey_id  # noqa: E402
+from drynx_amd.query import iter_rounds, new_survey_id  # noqa: E402
+from drynx_amd.rounds import max_base  # noqa: E402
 from drynx_amd.services.api import DrynxClient, serve_iterative  # noqa: E402
 from drynx_amd.services.local import local_cluster, make_iterative_survey, make_survey  # noqa: E402
 from drynx_amd.utils import timers  # noqa: E402
 
+# the reference's "Optimized (iterative) max" series (simul/test_data/graphs/TIFS/maxOpti.py:13): totals
+REFERENCE_MAX_ITERATIVE_S = {1_000: 5.6, 10_000: 7.6, 100_000: 9.6, 1_000_000: 11.3}
 CLASSIC_MAX_RANGE = 100_000
+OPERATION = {"max": "max", "quantile": "frequencyCount"}
 
 
 def parse():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--query", choices=sorted(OPERATION), required=True)
     ap.add_argument("--range", dest="value_range", type=int, default=1_000, help="values in [0, RANGE)")
     ap.add_argument("--bases", default="10,32,100,1000", help="comma-separated bases of the iterative search")
-    ap.add_argument("--quantile", default="1/2", help="num/den of the nearest-rank quantile")
-    ap.add_argument("--rows", type=int, default=100, help="records per DP")
+    ap.add_argument("--quantile", default="1/2", help="num/den of the nearest-rank quantile (--query quantile)")
+    ap.add_argument("--rows", type=int, default=100, help="records per DP (--query quantile)")
     ap.add_argument("--steps", type=int, default=5, help="timed searches / queries per run")
     ap.add_argument("--passes", type=int, default=2, help="times the whole list of runs is gone through")
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--device", default=None)
-    ap.add_argument("--no-classic", action="store_true", help="skip the one-shot frequencyCount")
+    ap.add_argument("--no-classic", action="store_true", help="skip the one-shot query")
     ap.add_argument("--encoder-iters", type=int, default=200, help="encoder calls per timed window (GPU only)")
     ap.add_argument("--out-dir", default=None, help="write range_<N>.json here")
     ap.set_defaults(cns=3, dps=10, vns=3)
@@ -72,9 +86,10 @@ def parse():
         args.num, args.den = int(num), int(den or 1)
     except ValueError:
         ap.error("--bases is a comma-separated list of integers, --quantile is num/den")
+    top = max_base(OPERATION[args.query])
     if args.passes < 1 or args.steps < 1 or args.rows < 1 or args.value_range < 2 or not args.base_list \
-            or any(not 2 <= b <= ITER_MAX_HIST_BASE for b in args.base_list):
-        ap.error(f"--passes, --steps and --rows at least 1, --range at least 2, bases in 2..{ITER_MAX_HIST_BASE}")
+            or any(not 2 <= b <= top for b in args.base_list):
+        ap.error(f"--passes, --steps and --rows at least 1, --range at least 2, bases in 2..{top}")
     if args.den < 1 or not 0 <= args.num <= args.den:
         ap.error("--quantile num/den with 0 <= num <= den")
     return args
@@ -111,19 +126,92 @@ def quantile_of_histogram(counts, num, den):
     raise RuntimeError("no records in the domain")
 
 
-def encoder_alone(args, device) -> dict:
-    """ms per call of the kernel pair on uniform records and on all-equal ones (device events)."""
+class MaxQuery:
+    """What ``--query max`` sets: bench.py's record count, (2, 1) ranges, the clear max."""
+    ranges = None  # make_iterative_survey's own (2, 1)
+    classic_ranges = [2, 1]
+    range_proof = {"u": 2, "l": 1}
+
+    def __init__(self, args):
+        cfg = bench.QUERY_CONFIGS["max"]
+        self.dps, self.rows = cfg["dps"], cfg["records"] // cfg["dps"]
+
+    def clear(self, comm, mine):
+        mx = comm.all_gather_object(max(mine, default=None))
+        return max(v for v in mx if v is not None)
+
+    def search(self, client, sq, base, on_round):
+        return client.send_iterative_extreme(sq, base, on_round=on_round)
+
+    def classic_value(self, vals):
+        return vals[0][0]
+
+    def head(self, N, want):
+        return {"clear_max": want}
+
+    def reference(self, N):
+        return {"reference": {"unary_s": bench.REFERENCE_MAX_UNARY_S.get(N),
+                              "iterative_s": REFERENCE_MAX_ITERATIVE_S.get(N),
+                              "source": "simul/test_data/graphs/TIFS/maxOpti.py:9-13"}}
+
+    probe_what = ("iter_round('max') (two launches + the plan upload) vs batch_values('max') at the same "
+                  "output width, device events, three windows each, alternating")
+
+    def probe_cases(self, rows, g, device):
+        for b in (10, 1000):
+            Z = torch.randint(0, b ** 2, (sum(rows), 1), generator=g, device=device)
+            yield f"width={b}", {"kernel_pair": lambda: nt.iter_round("max", Z, rows, 0, b ** 2 - 1, b, 0, 0),
+                                 "batch_values": lambda: enc.batch_values("max", Z, rows, 0, b - 1)}
+
+
+class QuantileQuery:
+    """What ``--query quantile`` sets: ``--rows`` records, (16, l) ranges, the clear nearest-rank quantile."""
+
+    def __init__(self, args):
+        self.dps, self.rows, self.num, self.den = args.dps, args.rows, args.num, args.den
+        l = 1
+        while 16 ** l <= self.rows:
+            l += 1
+        self.ranges = self.classic_ranges = [16, l]
+        self.range_proof = {"u": 16, "l": l}
+
+    def clear(self, comm, mine):
+        return nearest_rank([x for part in comm.all_gather_object(mine) for x in part], self.num, self.den)
+
+    def search(self, client, sq, base, on_round):
+        return client.send_iterative_quantile(sq, base, self.num, self.den, on_round=on_round)
+
+    def classic_value(self, vals):
+        return quantile_of_histogram([int(round(v)) for v in vals[0]], self.num, self.den)
+
+    def head(self, N, want):
+        return {"quantile": f"{self.num}/{self.den}", "clear_quantile": want}
+
+    def reference(self, N):
+        return {}
+
+    probe_what = ("iter_round('frequencyCount') (two launches + the plan upload), round 0 over base^2 values, "
+                  "uniform records vs every record equal, device events, three windows each, alternating")
+
+    def probe_cases(self, rows, g, device):
+        for b in (10, 1000, 4096):
+            R = b ** 2
+            Zu = torch.randint(0, R, (sum(rows), 1), generator=g, device=device)
+            Ze = torch.full((sum(rows), 1), R // 2, dtype=torch.int64, device=device)
+            yield f"base={b}", {"uniform": lambda: nt.iter_round("frequencyCount", Zu, rows, 0, R - 1, b, 0, 0),
+                                "all_equal": lambda: nt.iter_round("frequencyCount", Ze, rows, 0, R - 1, b, 0, 0)}
+
+
+QUERIES = {"max": MaxQuery, "quantile": QuantileQuery}
+
+
+def encoder_alone(args, query, device) -> dict:
+    """ms per call of the query's kernel-probe cases (device events)."""
     g = torch.Generator(device=device).manual_seed(7)
     rows = [100_000] * 10
-    out = {"records": "10 DPs x 100000", "calls_per_window": args.encoder_iters,
-           "what": "digit_histogram (two launches + the plan upload), round 0 over base^2 values, uniform records "
-                   "vs every record equal, device events, three windows each, alternating", "ms_per_call": {}}
-    for b in (10, 1000, 4096):
-        R = b ** 2
-        Zu = torch.randint(0, R, (sum(rows), 1), generator=g, device=device)
-        Ze = torch.full((sum(rows), 1), R // 2, dtype=torch.int64, device=device)
-        calls = {"uniform": lambda: nt.digit_histogram(Zu, rows, 0, R - 1, b, 0, 0),
-                 "all_equal": lambda: nt.digit_histogram(Ze, rows, 0, R - 1, b, 0, 0)}
+    out = {"records": "10 DPs x 100000", "calls_per_window": args.encoder_iters, "what": query.probe_what,
+           "ms_per_call": {}}
+    for label, calls in query.probe_cases(rows, g, device):
         ms = {k: [] for k in calls}
         for f in calls.values():
             for _ in range(5):
@@ -138,7 +226,7 @@ def encoder_alone(args, device) -> dict:
                 e.record()
                 torch.cuda.synchronize(device)
                 ms[k].append(round(a.elapsed_time(e) / args.encoder_iters, 5))
-        out["ms_per_call"][f"base={b}"] = ms
+        out["ms_per_call"][label] = ms
     return out
 
 
@@ -154,18 +242,15 @@ def main():
     device = comm.device
     if device.type == "cuda":
         torch.cuda.set_device(device)
-    N, n_dps, rows = args.value_range, args.dps, args.rows
-    l = 1
-    while 16 ** l <= rows:
-        l += 1
+    query, op_name = QUERIES[args.query](args), OPERATION[args.query]
+    N, n_dps, rows = args.value_range, query.dps, query.rows
     offsets = {"cn": 0, "vn": args.cns % world, "dp": (args.cns + args.vns) % world}
     cl, node = local_cluster(args.cns, n_dps, args.vns, comm=comm, device=device,
-                             workdir=tempfile.mkdtemp(prefix=f"drynx_quantile_iter_r{rank}_"), offsets=offsets)
-    g = torch.Generator(device=device).manual_seed(99 + rank)
+                             workdir=tempfile.mkdtemp(prefix=f"drynx_{args.query}_iter_r{rank}_"), offsets=offsets)
+    g = torch.Generator(device=device).manual_seed(99 + rank)  # bench.py's records
     node.dp_data = {dp.id: list(torch.randint(0, N, (1, rows), generator=g, device=device))
                     for dp in cl.local(rank, "dp")}
-    mine = [int(x) for cols in node.dp_data.values() for x in cols[0].cpu().tolist()]
-    want = nearest_rank([x for part in comm.all_gather_object(mine) for x in part], args.num, args.den)
+    want = query.clear(comm, [int(x) for cols in node.dp_data.values() for x in cols[0].cpu().tolist()])
     client = DrynxClient(node, device=device) if rank == 0 else None
     classic = not args.no_classic and N <= CLASSIC_MAX_RANGE
     names = [f"base={b}" for b in args.base_list] + (["classic"] if classic else [])
@@ -175,16 +260,17 @@ def main():
         for name in names:
             t0 = time.perf_counter()
             if name == "classic":
-                templates[name] = make_survey(client, cl, "frequencyCount", query_min=0, query_max=N - 1, rows=rows,
-                                              proofs=1, ranges=[16, l], thresholds=thresholds, sig_device=device)
+                templates[name] = make_survey(client, cl, op_name, query_min=0, query_max=N - 1, rows=rows, proofs=1,
+                                              ranges=query.classic_ranges, thresholds=thresholds, sig_device=device)
             else:
-                templates[name] = make_iterative_survey(client, cl, "frequencyCount", int(name[5:]), query_min=0,
-                                                        query_max=N - 1, rows=rows, proofs=1, ranges=[16, l],
-                                                        thresholds=thresholds, sig_device=device)
+                kw = {} if query.ranges is None else {"ranges": query.ranges}
+                templates[name] = make_iterative_survey(client, cl, op_name, int(name[5:]), query_min=0,
+                                                        query_max=N - 1, rows=rows, proofs=1, thresholds=thresholds,
+                                                        sig_device=device, **kw)
             sig_s[name] = round(time.perf_counter() - t0, 3)
 
     def one_step(name):
-        """-> (quantile, [blocks], [ms per round]) on rank 0."""
+        """-> (decoded value, [blocks], [ms per round]) on rank 0."""
         if name == "classic":
             if rank != 0:
                 node.run_survey(None)
@@ -192,15 +278,14 @@ def main():
             sq = copy.copy(templates[name])
             sq.SurveyID = new_survey_id()
             _, vals, res = client.send_survey_query(sq)
-            return quantile_of_histogram([int(round(v)) for v in vals[0]], args.num, args.den), [res.block], []
+            return query.classic_value(vals), [res.block], []
         if rank != 0:
             serve_iterative(node)
             return None
         sq = copy.copy(templates[name])
         sq.SurveyID = new_survey_id()
         marks = [time.perf_counter()]
-        value, rounds = client.send_iterative_quantile(sq, int(name[5:]), args.num, args.den,
-                                                       on_round=lambda *_: marks.append(time.perf_counter()))
+        value, rounds = query.search(client, sq, int(name[5:]), lambda *_: marks.append(time.perf_counter()))
         return value, [r.block for r in rounds], [round(1000 * (b - a), 2) for a, b in zip(marks, marks[1:])]
 
     def drop_tables():
@@ -241,17 +326,16 @@ def main():
                      "ms_per_round": round(sum(per_round) / len(per_round), 2) if per_round else None,
                      "round_ms": [rms for _, _, rms in steps],
                      "all_proofs_valid": ok, "result_ok": all(int(round(v)) == want for v, _, _ in steps)})
-    encoder = encoder_alone(args, device) if rank == 0 and device.type == "cuda" and world == 1 else None
+    encoder = encoder_alone(args, query, device) if rank == 0 and device.type == "cuda" and world == 1 else None
     node.close(remove=True)
     if rank != 0:
         return
-    out = {"tool": "bench_quantile_iter", "range": N, "quantile": f"{args.num}/{args.den}",
-           "steps_per_run": args.steps, "n_gpus": world, "device": device.type,
-           "order": [r["query"] for r in runs], "clear_quantile": want,
+    out = {"tool": "bench_iter", "query": args.query, "range": N, "steps_per_run": args.steps, "n_gpus": world,
+           "device": device.type, "order": [r["query"] for r in runs], **query.head(N, want),
            "config": {"cns": args.cns, "vns": args.vns, "dps": n_dps, "records_per_dp": rows,
-                      "range_proof": {"u": 16, "l": l}, "sigs": "random (per CN, per column)",
+                      "range_proof": query.range_proof, "sigs": "random (per CN, per column)",
                       "thresholds": [1, 1, 1, 0, 1]},
-           "signature_setup_s": sig_s, "runs": runs, "queries": {}}
+           **query.reference(N), "signature_setup_s": sig_s, "runs": runs, "queries": {}}
     for name in names:
         mine = [r for r in runs if r["query"] == name]
         per_run = [r["s_per_result"] for r in mine]
@@ -265,6 +349,9 @@ def main():
     it = {k: v for k, v in out["queries"].items() if k != "classic"}
     best = min(it, key=lambda k: it[k]["s_per_result"])
     out["best_base"] = {"query": best, "s_per_result": it[best]["s_per_result"]}
+    if args.query == "max":
+        ref = REFERENCE_MAX_ITERATIVE_S.get(N)
+        out["below_reference_iterative"] = None if ref is None else it[best]["s_per_result"] < ref
     if classic:
         out["iterative_over_classic"] = round(it[best]["s_per_result"] / out["queries"]["classic"]["s_per_result"], 4)
     out["all_proofs_valid"] = all(q["all_proofs_valid"] for q in out["queries"].values())
@@ -276,7 +363,7 @@ def main():
         with open(os.path.join(args.out_dir, f"range_{N}.json"), "w") as f:
             json.dump(out, f, indent=1)
     if not (out["all_proofs_valid"] and out["result_ok"]):
-        sys.exit("bench_quantile_iter: a proof was rejected or a decoded result is wrong")
+        sys.exit("bench_iter: a proof was rejected or a decoded result is wrong")
 
 
 if __name__ == "__main__":
