@@ -51,9 +51,13 @@ def survey_set_operation(a):
 
 def survey_run(a):
     """roster[0] is the CN (and the VN roster), roster[1:] are DPs; no proofs;
-    GroupBy {3,2,1}; 10 rows in [0, 256] (survey.go:93-132)."""
+    GroupBy {3,2,1}; 10 rows in [0, 256] (survey.go:93-132).  ``--group-by c1,c3
+    --cardinalities 3,2``, ``--where c2=1`` (repeatable) and ``--select c0`` fill
+    the query's SQL (``query.QuerySQL``); with a GROUP BY every group's key and
+    result are printed, one line each."""
     from ..crypto import oracle as O
-    from ..query import QueryDPDataGen, QueryDiffP, Roster, ServerIdentity, choose_operation
+    from ..query import (QueryDPDataGen, QueryDiffP, QuerySQL, Roster, ServerIdentity, WhereClear, check_parameters,
+                         choose_operation)
     from ..services.api import DrynxClient
     from ..services.server import RemoteNode
 
@@ -73,7 +77,28 @@ def survey_run(a):
     client = DrynxClient(RemoteNode(entry))  # the roster travels inside the SurveyQuery
     sq = client.generate_survey_query(roster, None, s2dp, id_to_pub, cfg["Survey"].get("Name"), op, None, None, 0,
                                       False, [0.0] * 5, QueryDiffP(), QueryDPDataGen([3, 2, 1], 10, 0, 256))
+    csv = lambda v: [x.strip() for x in (v or "").split(",") if x.strip()]  # noqa: E731
+    where = []
+    for term in a.where or []:
+        name, eq, value = term.partition("=")
+        if not eq:
+            raise SystemExit(f"--where {term}: expected COLUMN=VALUE")
+        where.append(WhereClear(name.strip(), value.strip()))
+    sq.Query.SQL = QuerySQL(Select=csv(a.select), Where=where, GroupBy=csv(a.group_by))
+    if sq.Query.SQL.GroupBy:
+        try:
+            sq.Query.DPDataGen.GroupByValues = [int(v) for v in csv(a.cardinalities)]
+        except ValueError:
+            raise SystemExit(f"--cardinalities {a.cardinalities}: integers, one per --group-by column")
+    elif a.cardinalities:
+        raise SystemExit("--cardinalities without --group-by")
+    if sq.Query.SQL and not check_parameters(sq, False):
+        raise SystemExit("the SQL part of the query is not valid (see the log)")
     groups, values, _ = client.send_survey_query(sq)
+    if sq.Query.SQL.GroupBy:  # real groups: one line each
+        for g, v in zip(groups, values):
+            print(g + ": " + " ".join(str(x) for x in v))
+        return
     first = values[0]
     if any(v != first for v in values):
         raise SystemExit(f"groups disagree: {values}")
@@ -99,7 +124,12 @@ def main(argv=None):
     p = sv.add_parser("set-operation")
     p.add_argument("operation")
     p.set_defaults(fn=survey_set_operation)
-    sv.add_parser("run").set_defaults(fn=survey_run)
+    p = sv.add_parser("run")
+    p.add_argument("--group-by", default="", help="columns to group by, e.g. c1,c3")
+    p.add_argument("--cardinalities", default="", help="values per --group-by column, e.g. 3,2")
+    p.add_argument("--where", action="append", help="COLUMN=VALUE, e.g. c2=1 (repeatable: a conjunction)")
+    p.add_argument("--select", default="", help="the operation's input columns, e.g. c0")
+    p.set_defaults(fn=survey_run)
     a = ap.parse_args(argv)
     a.fn(a)
     return 0

@@ -62,14 +62,16 @@ if __name__ == "__main__":  # python -m drynx_amd.models.datasets PCS file.txt [
     clean_file(a[0], a[1], a[3] if len(a) > 3 else None, a[2] if len(a) > 2 else "int")
 
 
-def load_dp_file(path: str, op, device="cpu"):
+def load_dp_file(path: str, op, device="cpu", query=None):
     """A data provider's records for ``op`` from a file (the file loader of
     ``server data-provider new file-loader PATH``): one record per line,
     values separated by commas.  Logistic regression reads the cleaned
     dataset layout ``label,f1,...,fd`` (``load_csv_dataset``, the reference's
     GetDataForDataProvider) -> (X float64 [n, d], y int64 [n]); every other
     operation takes the first NbrInput values of each record as int64
-    columns -> [column tensors] (the layout of ``generate_fake_data``)."""
+    columns -> [column tensors] (the layout of ``generate_fake_data``).  With
+    the ``query`` given and SQL in it, the columns of its record table are read
+    instead: 1 + the largest column it names (``query.sql_plan``)."""
     import numpy as np
     import torch
 
@@ -84,6 +86,10 @@ def load_dp_file(path: str, op, device="cpu"):
         return X.to(device), y.to(device)
     data = np.loadtxt(path, delimiter=",", dtype=np.float64, ndmin=2)
     n_in = max(1, int(op.NbrInput))
+    if query is not None and query.SQL:
+        from ..query import sql_plan
+
+        n_in = sql_plan(query).width
     if data.shape[1] < n_in:
         raise ValueError(f"{path}: {data.shape[1]} values per record, the operation reads {n_in}")
     if not np.all(data[:, :n_in] == np.round(data[:, :n_in])):

@@ -143,6 +143,8 @@ _SIGS = {
     "dx_rp_coeffs": [_P, _P, _P, _L],
     "dx_int_moments": [_I, _P, _P, _L, _I, _P, _L, _P, _I, _P, _P],
     "dx_iter_round": [_I, _P, _P, _L, _P, _L, _P, _L, _I, _L, _L, _L, _L, _L, _P, _P],
+    "dx_group_moments": [_I, _P, _P, _L, _I, _P, _L, _I, _P, _L, _P, _I, _P, _I, _P, _I, _L, _L, _P],
+    "dx_group_moments_max_cells": [],
     "dx_sha256_rows": [_I, _P, _P, _L, _L, _L, _L, _P],
     "dx_sha256_segments": [_I, _P, _P, _L, _L, _L, _P],
     "dx_g1_aff_to_uv": [_I, _P, _P, _L],
@@ -1162,6 +1164,96 @@ def int_moments(Z: torch.Tensor, seg_rows, pairs) -> torch.Tensor:
     partial = None if g else torch.empty((n_tiles, P), dtype=torch.int64)
     _call("dx_int_moments", g, s, _ptr(Zc), Zc.stride(0), C, _ptr(tiles), n_tiles, _ptr(pairs_t), P, _ptr(out),
           _ptr(partial))
+    return out
+
+
+GROUP_MOMENTS_MAX_KEYS = 4
+GROUP_MOMENTS_MAX_FILTERS = 8
+GROUP_MOMENTS_MAX_GROUPS = 1 << 24
+# LDS accumulator cells (group of the window x pair) of one launch: what half a
+# CU's 160 KiB leaves beside the staging area (csrc/kernels/dx_group_moments.hip
+# kMaxCells, exported as dx_group_moments_max_cells)
+GROUP_MOMENTS_MAX_CELLS = 5888
+
+
+def group_moments(Z: torch.Tensor, K: torch.Tensor | None, seg_rows, pairs, keys=(), filters=(),
+                  bins=None) -> torch.Tensor:
+    """K14d (csrc/kernels/dx_group_moments.hip): ``int_moments`` filtered and
+    grouped, ``out[dp, g, p] = sum over the rows i of segment dp with where(i)
+    and key(i) == g of Z[i, a_p] * Z[i, b_p]`` (mod 2^64) -> [n_dp, G, P] int64.
+
+    Z [rows, C], ``seg_rows`` and ``pairs`` are ``int_moments``' (C may be 0: only
+    the constant column, counts).  K [rows, CK] int64 holds the key and filter
+    columns and is read in place through its row stride (a view is fine; None
+    without keys and filters).  ``keys``: up to 4 ``(column of K, offset,
+    cardinality)``; a row's group is the mixed-radix number of ``K[i, column] -
+    offset`` over the cardinalities, first key most significant, and a row with
+    a digit outside ``[0, cardinality)`` is dropped; G is the product of the
+    cardinalities (1 without keys).  ``filters``: up to 8 ``(column of K,
+    value)``; a row counts if every one of its columns equals the value.
+    ``bins``: one more, innermost key triple beside the 4 -- the counted column
+    (x, QueryMin, R) of a frequency count, whose (group, bin) cells are groups.
+
+    One launch per window of ``GROUP_MOMENTS_MAX_CELLS // P`` consecutive
+    groups (the accumulators of a window live in LDS), no torch op and no host
+    work per record between the uploads and the output."""
+    assert Z.dtype == torch.int64 and Z.dim() == 2 and (Z.shape[1] == 0 or Z.stride(1) == 1)
+    C = Z.shape[1]
+    pr = np.asarray(pairs, dtype=np.int16).reshape(-1, 2)
+    if C > INT_MOMENTS_MAX_COLS or pr.size == 0 or pr.min() < 0 or pr.max() > C:
+        raise ValueError(f"group_moments: {C} columns, pairs out of range")
+    keys = [tuple(int(x) for x in k) for k in keys]
+    filters = [tuple(int(x) for x in f) for f in filters]
+    if len(keys) > GROUP_MOMENTS_MAX_KEYS or any(len(k) != 3 for k in keys):
+        raise ValueError(f"group_moments: {len(keys)} key columns (at most {GROUP_MOMENTS_MAX_KEYS} triples)")
+    if len(filters) > GROUP_MOMENTS_MAX_FILTERS or any(len(f) != 2 for f in filters):
+        raise ValueError(f"group_moments: {len(filters)} filter terms (at most {GROUP_MOMENTS_MAX_FILTERS} pairs)")
+    if bins is not None:
+        keys = keys + [tuple(int(x) for x in bins)]
+        if len(keys[-1]) != 3:
+            raise ValueError("group_moments: bins is one (column, offset, cardinality)")
+    CK = 0
+    if K is not None:
+        assert K.dtype == torch.int64 and K.dim() == 2 and (K.shape[1] <= 1 or K.stride(1) == 1)
+        if K.shape[0] != Z.shape[0]:
+            raise ValueError(f"group_moments: K has {K.shape[0]} rows, Z has {Z.shape[0]}")
+        CK = K.shape[1]
+    G = 1
+    for col, _, card in keys:
+        if card < 1 or card > GROUP_MOMENTS_MAX_GROUPS:
+            raise ValueError(f"group_moments: cardinality {card}")
+        G *= card
+    if G > GROUP_MOMENTS_MAX_GROUPS:
+        raise ValueError(f"group_moments: {G} groups (at most {GROUP_MOMENTS_MAX_GROUPS})")
+    for col in [k[0] for k in keys] + [f[0] for f in filters]:
+        if not 0 <= col < CK:
+            raise ValueError(f"group_moments: column {col} of a {CK}-column key matrix")
+    counts = np.asarray(seg_rows, dtype=np.int64).reshape(-1)
+    n_dp, P = len(counts), pr.shape[0]
+    if counts.sum() != Z.shape[0] or (n_dp and counts.min() < 0):
+        raise ValueError(f"group_moments: segments cover {counts.sum()} rows, Z has {Z.shape[0]}")
+    out = torch.zeros((n_dp, G, P), dtype=torch.int64, device=Z.device)
+    gw = max(1, GROUP_MOMENTS_MAX_CELLS // P)
+    # a tile zeroes and flushes its window's cells: it streams at least as many rows
+    plan, _ = _tile_plan(counts, min(min(G, gw) * P, 2048))
+    n_tiles = len(plan)
+    if n_tiles == 0:
+        return out
+    Zc = Z if C == 0 else Z.contiguous()
+    tiles = _upload(plan, Z.device)
+    pairs_t = _upload(pr, Z.device)
+    kd = np.ascontiguousarray(np.asarray(keys, dtype=np.int64).reshape(-1))
+    fd = np.ascontiguousarray(np.asarray(filters, dtype=np.int64).reshape(-1))
+    g, s = _ctx(Zc, K)
+    for g0 in range(0, G, gw):
+        rc = _raw_call("dx_group_moments", g, s, _ptr(Zc), Zc.stride(0) if C else 0, C,
+                       _ptr(K, strided=True), K.stride(0) if CK else 0, CK, _ptr(tiles), n_tiles, _ptr(pairs_t), P,
+                       kd.ctypes.data_as(_P), len(keys), fd.ctypes.data_as(_P), len(filters), g0, min(gw, G - g0),
+                       _ptr(out))
+        if rc == -2:
+            raise ValueError("group_moments: the entry refused its arguments")
+        if rc != 0:
+            raise RuntimeError(f"native op dx_group_moments failed (rc={rc})")
     return out
 
 

@@ -220,6 +220,57 @@ def batch_values(name: str, Z: torch.Tensor, seg_rows, qmin: int = 0, qmax: int 
     raise ValueError(f"{name} has no batched encoder")
 
 
+COUNT_OPS = ("frequencyCount", "union", "inter", "min", "max")
+
+
+def batch_values_sql(name: str, Z: torch.Tensor, K: torch.Tensor, seg_rows, sql_plan, qmin: int = 0,
+                     qmax: int = 0) -> torch.Tensor:
+    """[n_dp, ng, n_out] int64 outputs of every (DP, group) cell of a batch for
+    a query with ``Query.SQL``, on Z's device: ``batch_values`` over the records
+    that pass the WHERE conjunction, per GROUP BY group (ng = 1 without one).
+
+    Z [rows, n_in] holds the operation's input columns (the SQL ``Select``) as
+    ``batch_values`` takes them, K [rows, width] the DPs' record tables, which
+    the key and filter columns of ``sql_plan`` (``query.SQLPlan``) index; both
+    stack the DPs' records back to back (``seg_rows[g]`` rows for DP g).  One
+    K14d launch per group window (``native.group_moments``) for every DP.
+
+    Moments: the sums of K14's pair list per cell.  frequencyCount: the counted
+    column is one more innermost key (x, qmin, R), so a (group, bin) cell is a
+    group of a counting query.  union / inter / min / max are derived from those
+    counts on the device: union = count > 0, inter its complement, min bit_i =
+    [i >= first occupied bin], max (inverted AND) bit_i = [i < last occupied
+    bin]; the min and max rows of a cell without records are all zero, as an
+    empty DP's are in ``batch_values``.  NOTE: with SQL, records outside [qmin,
+    qmax] are DROPPED for these four operations as frequencyCount drops them
+    (``batch_values`` lets an out-of-domain extreme saturate min / max)."""
+    from .. import native as nt
+
+    keys = [(c, 0, v) for c, v in sql_plan.group_by]
+    filters = list(sql_plan.where)
+    if name in MOMENT_OPS:
+        if name == "MLeval":
+            Z = torch.stack([Z[:, 0], Z[:, 1] - Z[:, 0]], dim=1)
+        elif name in ("sum", "mean", "variance"):
+            Z = Z[:, :1]
+        return nt.group_moments(Z.contiguous(), K, seg_rows, moment_pairs(name, Z.shape[1]), keys, filters)
+    if name not in COUNT_OPS:
+        raise ValueError(f"{name} has no SQL encoder")
+    n = qmax - qmin + 1
+    cnt = nt.group_moments(Z[:, :0], K, seg_rows, [(0, 0)], keys, filters, bins=(sql_plan.select[0], qmin, n))
+    cnt = cnt.reshape(len(seg_rows), -1, n)
+    if name == "frequencyCount":
+        return cnt
+    occ = (cnt > 0).to(torch.int64)
+    if name == "union":
+        return occ
+    if name == "inter":
+        return 1 - occ
+    if name == "min":  # an occupied bin at or below i
+        return (occ.cumsum(2) > 0).to(torch.int64)
+    return ((occ.flip(2).cumsum(2).flip(2) - occ) > 0).to(torch.int64)  # max: an occupied bin above i
+
+
 def iterative_values(operation: Operation, Z: torch.Tensor, seg_rows, base: int, rnd: int, prefix: int):
     """[n_dp, base] int64 values of one round of an iterative query
     (``SurveyQuery.IterBase``), by operation.  min / max: per DP the 0/1 values
@@ -367,14 +418,17 @@ def decode_values(name: str, vals: list, operation: Operation) -> list:
     """Decoders that only need the decrypted integers (encode_decode.go:163-231)."""
     if name == "sum":
         return [float(vals[0])]
+    nan = float("nan")  # a group without records (a SQL group nobody populates): N = 0
     if name == "mean":
-        return [vals[0] / vals[1]]
+        return [vals[0] / vals[1] if vals[1] else nan]
     if name == "variance":
+        if not vals[1]:
+            return [nan]
         mean = vals[0] / vals[1]
         return [vals[2] / vals[1] - mean * mean]
     if name == "cosim":
         sa, sb, saa, sbb, sab = vals
-        return [sab / ((saa ** 0.5) * (sbb ** 0.5))]
+        return [sab / ((saa ** 0.5) * (sbb ** 0.5)) if saa and sbb else nan]
     if name == "frequencyCount":
         return [float(v) for v in vals]
     if name == "lin_reg":

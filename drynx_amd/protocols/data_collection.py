@@ -21,7 +21,7 @@ import torch
 from ..crypto import elgamal as eg
 from ..ops import encoding as enc
 from ..parallel import ec_collectives as ec
-from ..query import lr_nbr_outputs
+from ..query import lr_nbr_outputs, sql_plan
 from ..utils import timers
 
 
@@ -66,6 +66,24 @@ def generate_fake_data(op, nbr_rows: int, lo: int, hi: int, device, gen: torch.G
     return list(t.unbind(0))
 
 
+def generate_sql_table(sq, dp_id: str, plan) -> torch.Tensor:
+    """[rows, plan.width] int64 record table (host) a DP generates for a query
+    with SQL.  Columns below NbrInput are ``generate_fake_data``'s draws for the
+    DP's seed, unchanged; the columns from NbrInput on come, in column order,
+    from a second generator seeded from the same id: a ``GroupBy[i]`` column is
+    uniform in [0, V_i), every other one uniform in [0, 3]."""
+    q = sq.Query
+    g = q.DPDataGen
+    n_in, n_rows = max(1, q.Operation.NbrInput), max(1, g.GenerateRows)
+    gen = torch.Generator().manual_seed(_seed(data_seed_id(sq), dp_id))
+    t = torch.randint(g.GenerateDataMin, g.GenerateDataMax + 1, (n_in, n_rows), generator=gen, dtype=torch.int64)
+    gen2 = torch.Generator().manual_seed(_seed(data_seed_id(sq) + "/sql", dp_id))
+    cards = dict(plan.group_by)
+    extra = [torch.randint(0, cards.get(c, 4), (n_rows,), generator=gen2, dtype=torch.int64)
+             for c in range(n_in, plan.width)]
+    return torch.cat([t, torch.stack(extra)] if extra else [t])[: plan.width].t()
+
+
 def generate_lr_data(params, device, gen: torch.Generator):
     """Synthetic LR records (data_collection_protocol.go:226-241 dummy rows):
     features uniform in [0, 4) as float64, labels uniform {0,1}; generated on
@@ -87,6 +105,8 @@ def dp_encode(ctx, sq, dp, sync_timer: bool = True) -> dict:
     stacked CipherVector (groups x NbrOutput), per-group proof batches, clear values."""
     q = sq.Query
     op = q.Operation
+    if q.SQL:
+        raise ValueError(f"{op.NameOp}: a query with SQL is encoded by the batched encoders only")
     device = ctx.device
     pk = eg.pk_table(sq.RosterServers.aggregate(), device)
     gen = torch.Generator().manual_seed(_seed(data_seed_id(sq), dp.id))
@@ -155,11 +175,18 @@ def dp_encode_batch(ctx, sq, dps: list) -> dict:
     if op.NameOp == "logistic regression":
         return _encode_batch_tail(ctx, sq, dps, _lr_values(ctx, sq, dps, device), groups, pk)
     n_in = max(1, op.NbrInput)
+    plan = sql_plan(q)  # None: a query without SQL
     mats, rows = [], []
     for dp in dps:
         if ctx.dp_data and dp.id in ctx.dp_data:
             cols = [enc._t(c, device).reshape(-1).to(torch.int64) for c in ctx.dp_data[dp.id]]
+            if plan is not None:
+                if len(cols) < plan.width:
+                    raise ValueError(f"DP {dp.id} has {len(cols)} record columns, the SQL query reads {plan.width}")
+                cols = cols[: plan.width]
             mats.append(torch.stack(cols, dim=1))
+        elif plan is not None:
+            mats.append(generate_sql_table(sq, dp.id, plan))
         else:  # generate_fake_data's draw, kept on the host until the one upload below
             gen = torch.Generator().manual_seed(_seed(data_seed_id(sq), dp.id))
             t = torch.randint(g.GenerateDataMin, g.GenerateDataMax + 1, (n_in, max(1, g.GenerateRows)), generator=gen,
@@ -172,7 +199,11 @@ def dp_encode_batch(ctx, sq, dps: list) -> dict:
             Z = Z.pin_memory().to(device, non_blocking=True)
     else:
         Z = torch.cat([m.to(device) for m in mats]).contiguous()
-    if sq.IterBase:  # one round of an iterative query: [n_dp, IterBase] from the K14b (min/max) or K14c (counts) pair
+    if plan is not None:  # WHERE / GROUP BY: [n_dp, ng, n_out] from K14d, the table its key and filter columns
+        sel = plan.select
+        Zv = Z[:, sel[0]: sel[0] + len(sel)] if sel == list(range(sel[0], sel[0] + len(sel))) else Z[:, sel]
+        vals = enc.batch_values_sql(op.NameOp, Zv, Z, rows, plan, op.QueryMin, op.QueryMax)
+    elif sq.IterBase:  # one round of an iterative query: [n_dp, IterBase] from the K14b (min/max) or K14c (counts) pair
         vals = enc.iterative_values(op, Z, rows, sq.IterBase, sq.IterRound, sq.IterPrefix)
     else:
         vals = enc.batch_values(op.NameOp, Z, rows, op.QueryMin, op.QueryMax)  # [n_dp, n_out]
@@ -215,17 +246,24 @@ def _lr_values(ctx, sq, dps: list, device) -> torch.Tensor:
 def _encode_batch_tail(ctx, sq, dps: list, vals: torch.Tensor, groups, pk) -> dict:
     """Shared tail of ``dp_encode_batch``: one encryption launch for every
     (DP, group, output), CuttingFactor replication, one host copy, the proof
-    batches per DP."""
+    batches per DP.  ``vals`` [n_dp, n_out] is replicated over the groups (a
+    query without GROUP BY); [n_dp, ng, n_out] carries every group's own values
+    (and [n_dp, 1, n_out] is replicated like the 2-D form)."""
     q = sq.Query
     op = q.Operation
     device = torch.device(ctx.device)
     ng, cf = len(groups), q.CuttingFactor
-    n_dp, n_out = vals.shape
+    if vals.dim() == 3 and vals.shape[1] == 1:
+        vals = vals[:, 0]
+    grouped = vals.dim() == 3
+    if grouped and vals.shape[1] != ng:
+        raise ValueError(f"{vals.shape[1]} groups encoded, the query announces {ng}")
+    n_dp, n_out = vals.shape[0], vals.shape[-1]
     with_proofs = _with_proofs(q)
     bits = op.NameOp in enc.BIT_OPS and not with_proofs
     # one fresh encryption per (DP, group, output); CuttingFactor replicates a
     # group's ciphertexts cf times (same randomness), as dp_encode does
-    cv, r = enc.encrypt_batch(pk, vals[:, None, :].expand(n_dp, ng, n_out), bits)
+    cv, r = enc.encrypt_batch(pk, vals if grouped else vals[:, None, :].expand(n_dp, ng, n_out), bits)
     rep = max(1, cf or 1)
     idx = (torch.arange(ng, device=device)[:, None, None] * n_out
            + torch.arange(n_out, device=device)[None, None, :]).expand(ng, rep, n_out).reshape(-1)
@@ -238,17 +276,17 @@ def _encode_batch_tail(ctx, sq, dps: list, vals: torch.Tensor, groups, pk) -> di
         us, ls, offs = enc._ranges_uvl(q.Ranges, n_out)
     out = {}
     for i, dp in enumerate(dps):
-        v = host[i]
+        v = host[i] if grouped else [host[i]] * ng  # every group's values
         proofs = []
         if with_proofs:
             base = i * per_dp
             for j in range(ng):
                 lo = base + j * n_out
-                proofs.append(enc.CreateProofBatch(list(v), r[lo: lo + n_out], cv[lo: lo + n_out], us, ls,
-                                                   list(range(n_out)), offs, vals[i]))
+                proofs.append(enc.CreateProofBatch(list(v[j]), r[lo: lo + n_out], cv[lo: lo + n_out], us, ls,
+                                                   list(range(n_out)), offs, vals[i, j] if grouped else vals[i]))
         else:
             proofs = [None] * ng
-        out[dp.id] = {"cv": eg.CipherVector(K[i], C[i]), "proofs": proofs, "clear": [list(v) for _ in groups],
+        out[dp.id] = {"cv": eg.CipherVector(K[i], C[i]), "proofs": proofs, "clear": [list(v[j]) for j in range(ng)],
                       "n_groups": ng}
     return out
 

@@ -154,6 +154,113 @@ class Operation:
 
 
 @dataclass
+class WhereClear:
+    """One equality of a WHERE clause (structs.go WhereQueryAttributeClear):
+    column ``Name`` == int(``Value``)."""
+    Name: str = ""
+    Value: str = ""
+
+
+@dataclass
+class QuerySQL:
+    """structs.go:168-193 QuerySQL ("if real DB at data providers").  The
+    reference declares it and never reads it; the semantics are ours:
+
+    * a column name is ``c<k>``, the zero-based column k < 64 of a DP's record table;
+    * ``Select``: the NbrInput columns the operation reads, in its input order
+      (empty: c0 .. c{NbrInput-1});
+    * ``Where``: a conjunction of at most 8 equalities column == int(Value);
+      ``Predicate`` must stay empty (only the conjunction is defined);
+    * ``GroupBy``: at most 4 columns; ``DPDataGen.GroupByValues[i]`` is the
+      cardinality V_i of ``GroupBy[i]`` (product at most 4096), a record belongs
+      to the group of its values in those columns, in ``all_possible_groups``
+      order, and a record with a value outside [0, V_i) is dropped;
+    * ``Where`` without ``GroupBy``: the filtered answer is replicated over the
+      groups of ``GroupByValues`` as an unfiltered one is.
+
+    All empty = the query without SQL, in every respect."""
+    Select: list = field(default_factory=list)
+    Where: list = field(default_factory=list)
+    Predicate: str = ""
+    GroupBy: list = field(default_factory=list)
+
+    def __bool__(self):
+        return bool(self.Select or self.Where or self.Predicate or self.GroupBy)
+
+
+SQL_MAX_COLUMNS = 64
+SQL_MAX_WHERE = 8
+SQL_MAX_GROUP_BY = 4
+SQL_MAX_GROUPS = 4096
+SQL_OPERATIONS = ("sum", "mean", "variance", "cosim", "lin_reg", "MLeval", "frequencyCount", "union", "inter", "min",
+                  "max")
+
+
+def sql_column(name) -> int:
+    """Index k of the column name ``c<k>``; ValueError for anything else."""
+    if not isinstance(name, str) or len(name) < 2 or name[0] != "c" or not name[1:].isdigit() \
+            or not name[1:].isascii() or (len(name) > 2 and name[1] == "0"):
+        raise ValueError(f"malformed column name {name!r} (c<k>)")
+    k = int(name[1:])
+    if k >= SQL_MAX_COLUMNS:
+        raise ValueError(f"column {name} outside c0..c{SQL_MAX_COLUMNS - 1}")
+    return k
+
+
+@dataclass
+class SQLPlan:
+    """A checked QuerySQL in column indices: ``select`` (the operation's input
+    columns), ``where`` [(column, value)], ``group_by`` [(column, cardinality)]
+    and the table ``width`` (1 + the largest referenced column)."""
+    select: list
+    where: list
+    group_by: list
+    width: int
+
+
+def sql_plan(q: "Query") -> Optional[SQLPlan]:
+    """The plan of a query's SQL part, None when it has none.  Raises
+    ValueError with the violated rule (``check_parameters`` reports it)."""
+    sql = q.SQL
+    if not sql:
+        return None
+    n_in = max(1, q.Operation.NbrInput)
+    if sql.Predicate:
+        raise ValueError("SQL predicate set: only the conjunction of Where equalities is defined")
+    select = [sql_column(n) for n in sql.Select] if sql.Select else list(range(n_in))
+    if len(select) != n_in:
+        raise ValueError(f"SQL select lists {len(select)} columns, the operation reads {n_in}")
+    if len(sql.Where) > SQL_MAX_WHERE:
+        raise ValueError(f"SQL where has more than {SQL_MAX_WHERE} terms")
+    where = []
+    for w in sql.Where:
+        col = sql_column(w.Name)
+        v = str(w.Value).strip()
+        if not (v[1:] if v[:1] in "+-" else v).isdigit() or not v.isascii():
+            raise ValueError(f"SQL where value {w.Value!r} is not an integer")
+        if not -(1 << 63) <= int(v) < 1 << 63:
+            raise ValueError(f"SQL where value {w.Value!r} is not an int64")
+        where.append((col, int(v)))
+    group_by = []
+    if sql.GroupBy:
+        if len(sql.GroupBy) > SQL_MAX_GROUP_BY:
+            raise ValueError(f"SQL group by has more than {SQL_MAX_GROUP_BY} columns")
+        cards = list(q.DPDataGen.GroupByValues or [])
+        if len(cards) != len(sql.GroupBy):
+            raise ValueError("GroupByValues does not give one cardinality per SQL group-by column")
+        total = 1
+        for name, v in zip(sql.GroupBy, cards):
+            if not isinstance(v, int) or isinstance(v, bool) or v < 1:
+                raise ValueError("a SQL group-by cardinality below 1")
+            total *= v
+            group_by.append((sql_column(name), v))
+        if total > SQL_MAX_GROUPS:
+            raise ValueError(f"SQL group by over {total} groups (at most {SQL_MAX_GROUPS})")
+    width = 1 + max(select + [c for c, _ in where] + [c for c, _ in group_by])
+    return SQLPlan(select, where, group_by, width)
+
+
+@dataclass
 class Query:
     Operation: Operation = field(default_factory=Operation)
     Ranges: Optional[list] = None  # list of [u, l] (optionally [u, l, offset])
@@ -164,6 +271,7 @@ class Query:
     IVSigs: QueryIVSigs = field(default_factory=QueryIVSigs)
     RosterVNs: Optional[Roster] = None
     CuttingFactor: int = 0
+    SQL: QuerySQL = field(default_factory=QuerySQL)
 
 
 @dataclass
@@ -259,6 +367,8 @@ def _to_jsonable(obj):
                 out[f.name] = {k: ([s.to_dict() for s in lst] if lst is not None else None) for k, lst in v.items()}
             elif f.name == "InputValidationSigs":
                 out[f.name] = None if v is None else [[s.to_dict() for s in row] for row in v]
+            elif isinstance(v, QuerySQL) and not v:
+                continue  # an empty SQL is the dict of a query without the field
             else:
                 out[f.name] = _to_jsonable(v)
         return out
@@ -267,6 +377,16 @@ def _to_jsonable(obj):
     if isinstance(obj, dict):
         return {k: _to_jsonable(v) for k, v in obj.items()}
     return obj
+
+
+def sql_from_dict(d) -> QuerySQL:
+    """QuerySQL of its dict (JSON control plane or decoded wire message); a
+    peer without the field (None, {}) reads as the empty SQL."""
+    d = d or {}
+    return QuerySQL(Select=[str(s) for s in d.get("Select") or []],
+                    Where=[WhereClear(str(w.get("Name", "")), str(w.get("Value", ""))) for w in d.get("Where") or []],
+                    Predicate=str(d.get("Predicate") or ""),
+                    GroupBy=[str(s) for s in d.get("GroupBy") or []])
 
 
 def _survey_from_dict(d: dict) -> SurveyQuery:
@@ -287,6 +407,7 @@ def _survey_from_dict(d: dict) -> SurveyQuery:
         IVSigs=QueryIVSigs(**ivs),
         RosterVNs=Roster.from_dict(q["RosterVNs"]) if q.get("RosterVNs") is not None else None,
         CuttingFactor=q.get("CuttingFactor", 0),
+        SQL=sql_from_dict(q.get("SQL")),
     )
     return SurveyQuery(
         SurveyID=d.get("SurveyID", ""),
@@ -385,6 +506,7 @@ def check_parameters(sq: SurveyQuery, diffp: bool) -> bool:
             if len(lrp.InitialWeights or []) not in (0, D, max(1, nt) * D):
                 msg.append("initial weights are neither empty, one vector of d + 1 nor one per target")
     msg += _check_iterative(sq)
+    msg += _check_sql(sq)
     if q.Operation.QueryMin != q.DPDataGen.GenerateDataMin or q.Operation.QueryMax != q.DPDataGen.GenerateDataMax:
         msg.append("min or max are inconsistent at DP and operations")
     for m in msg:
@@ -431,6 +553,30 @@ def _check_iterative(sq: SurveyQuery) -> list:
             msg.append("an iterative frequencyCount round with (0, 0) among other ranges")
     elif q.Proofs and (q.Ranges is None or not _ranges_bits(q.Ranges)):
         msg.append("iterative rounds with proofs need (2, 1) ranges")
+    return msg
+
+
+def _check_sql(sq: SurveyQuery) -> list:
+    """Rules of a non-empty ``Query.SQL`` (see QuerySQL); nothing when it is empty."""
+    q = sq.Query
+    if not q.SQL:
+        return []
+    msg = []
+    name = q.Operation.NameOp
+    if name in ("bool_AND", "bool_OR"):
+        msg.append(f"SQL with {name}: a DP's bit is its first record, not a statistic of its records")
+    elif name == "logistic regression":
+        msg.append("SQL with logistic regression: its records are float features, not table columns")
+    elif name not in SQL_OPERATIONS:
+        msg.append(f"SQL with the operation {name}")
+    if sq.IterBase:
+        msg.append("SQL with iterative rounds")
+    if q.CuttingFactor != 0:
+        msg.append("SQL with a cutting factor")
+    try:
+        sql_plan(q)
+    except ValueError as e:
+        msg.append(str(e))
     return msg
 
 

@@ -68,15 +68,24 @@ class DrynxClient:
     # ------------------------------------------------------------------ execution
     def send_survey_query(self, sq: SurveyQuery):
         """SendSurveyQuery: run the survey, decode every group.  Returns
-        (group keys, list of decoded float vectors, SurveyResult)."""
+        (group keys, list of decoded float vectors, SurveyResult).  The key of
+        group g is ``str(g)``; with a SQL GROUP BY it is the group's column
+        values as the reference prints them (fmt.Sprint of a slice, "[0 1]"),
+        in ``all_possible_groups`` order."""
         op = sq.Query.Operation
+        keys = None
+        if sq.Query.SQL.GroupBy:
+            from ..protocols.data_collection import all_possible_groups
+
+            keys = ["[" + " ".join(str(v) for v in g) + "]"
+                    for g in all_possible_groups(sq.Query.DPDataGen.GroupByValues)]
 
         def decode_all(partial):
             groups, values = [], []
             self.last_plaintexts = []
             with timers.timed("Decode"):
                 for g, cv in enumerate(partial.groups()):
-                    groups.append(str(g))
+                    groups.append(keys[g] if keys is not None else str(g))
                     values.append(self.decode(cv.to(self.device), op))
             return groups, values
 

@@ -452,7 +452,8 @@ class NodeServer:
             return
         from ..models.datasets import load_dp_file
 
-        node.dp_data[f"dp:{self.address}"] = load_dp_file(self.dp_source["Path"], sq.Query.Operation, node.device)
+        node.dp_data[f"dp:{self.address}"] = load_dp_file(self.dp_source["Path"], sq.Query.Operation, node.device,
+                                                         sq.Query)
 
     def _ensure_node(self, roles: dict):
         from .service import DrynxNode

@@ -17,7 +17,7 @@ import uuid
 
 from ..crypto import oracle as O
 from ..query import (LogisticRegressionParameters, Operation, PublishSignatureBytes, Query, QueryDiffP,
-                     QueryDPDataGen, QueryIVSigs, Roster, ServerIdentity, SurveyQuery)
+                     QueryDPDataGen, QueryIVSigs, Roster, ServerIdentity, SurveyQuery, sql_from_dict)
 from . import onet
 
 
@@ -82,7 +82,9 @@ def survey_query_to_msg(sq: SurveyQuery) -> dict:
                        "InputValidationSize1": ivs.InputValidationSize1,
                        "InputValidationSize2": ivs.InputValidationSize2},
             "RosterVNs": roster_to_msg(q.RosterVNs) if q.RosterVNs is not None else None,
-            "SQL": {},
+            # (every field empty encodes to the empty message a query without SQL sends)
+            "SQL": {"Select": list(q.SQL.Select), "Where": [{"Name": w.Name, "Value": w.Value} for w in q.SQL.Where],
+                    "Predicate": q.SQL.Predicate, "GroupBy": list(q.SQL.GroupBy)},
             "CuttingFactor": q.CuttingFactor,
         },
         "IDtoPublic": {k: _pt(p) for k, p in sq.IDtoPublic.items()},
@@ -129,6 +131,7 @@ def survey_query_from_msg(d: dict) -> SurveyQuery:
                                ivs.get("InputValidationSize2", 0)),
             RosterVNs=roster_from_msg(q["RosterVNs"]) if q.get("RosterVNs") is not None else None,
             CuttingFactor=q.get("CuttingFactor", 0),
+            SQL=sql_from_dict(q.get("SQL")),  # absent (a peer without the field) reads as empty
         ),
         IDtoPublic={k: _unpt(v) for k, v in d["IDtoPublic"].items()},
         Threshold=d["Threshold"],
