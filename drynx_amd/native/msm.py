@@ -4,27 +4,29 @@ multi-exponentiation, the G1 MSM of the D-check and the G2 MSM of the R side
 
   runs     ``_runs``: bucket keys of every (entry, window), sorted, and every
            bucket's run in the sorted entries;
-  plan     ``_counted_plan`` (one host sync, arbitrary groups) or
-           ``_device_layout`` (shape-derived, no sync): the sorted ids ``bk`` of
-           the buckets that carry a value and the slice passes that reduce the
-           sorted entries to one row per such bucket (``_reduce``, given the
-           group's two slice operations);
-  weights  ``_g1_weight_plan`` / ``_chunk_weight_plan``: digit times bucket,
-           summed per (group, window);
-  finish   Horner over the windows.
+  plan     ``CountedPlan`` (one host sync, arbitrary groups) or the cached
+           ``DeviceLayout`` (shape-derived, no sync): the sorted ids of the
+           buckets that carry a value, the slice passes that reduce the sorted
+           entries to one row per such bucket (``_reduce``, given the group's
+           two slice operations) and the weights record, built with the plan;
+  weights  digit times bucket, summed per (group, window), the same stage for
+           either plan: ``DigitWeights`` (G1) or ``ChunkWeights`` (G2, GT);
+  finish   Horner over the windows of a ``Handle``.
 
 ``drynx_amd.native`` re-exports the public names.
 """
 from __future__ import annotations
 
 import threading
+from dataclasses import dataclass, field, fields
+from functools import partial
 
 import numpy as np
 
 import torch
 
-from . import (_call, _ctx, _gt_prod_level, _pow2_scalar, _ptr, _raw_call, _rows, _upload, g1_mul, gt_mul, gt_one,
-               gt_pi, gt_pow, gt_prod)
+from . import (_call, _ctx, _pow2_scalar, _ptr, _raw_call, _rows, _upload, g1_mul, gt_mul, gt_one, gt_pi, gt_pow,
+               gt_prod)
 
 _ME_SLICE = 8      # entries per thread in each segmented-product pass
 # entries per lane pair in the first pass over torus images (gt_beta_slice_prod): the first factor of a
@@ -84,6 +86,9 @@ def g2_slice_sum(src: torch.Tensor, idx, start: torch.Tensor, length: torch.Tens
     return out
 
 
+_g2_jac_sum = partial(g2_slice_sum, src_aff=False)      # over Jacobian rows: every level but the first
+
+
 def gt_chunk_weight(B: torch.Tensor, d: torch.Tensor, start: torch.Tensor, length: torch.Tensor,
                     base: torch.Tensor) -> torch.Tensor:
     """out[ch] = prod_{i in chunk ch} B[i]^d[i] over digit-sorted GT buckets
@@ -112,9 +117,9 @@ def g2_chunk_weight(B_jac: torch.Tensor, d: torch.Tensor, start: torch.Tensor, l
     return out
 
 
-# The two slice operations of each group, for ``_reduce``: the first level
-# reads the source rows through the sorted item index, every next level reads
-# the level before.  The groups' index types and row periods stay in here.
+# The two slice operations of each group, for ``_reduce``: ``first(start, len)`` reads the source rows through the
+# sorted item index, ``next(cur, None, start, len)`` (the group's slice kernel) the level before.  The groups' index
+# types and row periods stay in here.
 def _gt_ops(a: torch.Tensor, items: torch.Tensor, item_split: tuple | None = None):
     """Entry i reads a[i % n] (n = rows of a); with ``item_split`` = (s, q)
     entry i >= s reads a[(i - s) % q].  The kernel takes int64 premapped rows.
@@ -130,18 +135,17 @@ def _gt_ops(a: torch.Tensor, items: torch.Tensor, item_split: tuple | None = Non
     else:
         it = it % n
     it = it.contiguous()
-    return (lambda st, ln: first(a, it, st, ln)), (lambda cur, st, ln: gt_slice_prod(cur, None, st, ln))
+    return (lambda st, ln: first(a, it, st, ln)), gt_slice_prod
 
 
 def _g1_ops(P_jac: torch.Tensor, items: torch.Tensor):
     P_jac, it = P_jac.contiguous(), items.to(torch.int64)
-    return (lambda st, ln: g1_slice_sum(P_jac, it, st, ln)), (lambda cur, st, ln: g1_slice_sum(cur, None, st, ln))
+    return (lambda st, ln: g1_slice_sum(P_jac, it, st, ln)), g1_slice_sum
 
 
 def _g2_ops(P_aff: torch.Tensor, items: torch.Tensor, m: int):
     """Entry i reads the affine row P[i % m] (int32 index, modulus in the kernel)."""
-    return (lambda st, ln: g2_slice_sum(P_aff, items, st, ln, True, m)), \
-        (lambda cur, st, ln: g2_slice_sum(cur, None, st, ln, False))
+    return (lambda st, ln: g2_slice_sum(P_aff, items, st, ln, True, m)), _g2_jac_sum
 
 
 # ----------------------------------------------------------------------------- runs
@@ -231,11 +235,37 @@ def _segment_passes_dev(counts, dev, first_slice: int | None = None):
     return passes
 
 
-def _counted_plan(k: torch.Tensor, group, n_groups: int, W: int, c: int, first_slice: int | None = None) -> dict:
-    """Plan from the buckets' actual counts: ONE host sync (the counts), any
-    grouping.  ``bk``: the non-empty buckets; ``passes``: segmented slices
-    down to one value per such bucket (``_reduce``); ``item``: the sorted
-    entries without the zero-digit sentinels."""
+class _Record:
+    """Base of the records: a field is also read by name, ``r["W"]`` (the spelling of the dicts they
+    replace, which tests and tools outside this module still use), and each knows its tensors."""
+
+    def __getitem__(self, name: str):
+        return getattr(self, name)
+
+    def tensors(self, x=None):
+        """Every tensor the record reaches: its fields, through lists, tuples and nested records."""
+        for y in [getattr(self, f.name) for f in fields(self)] if x is None else x:
+            if isinstance(y, torch.Tensor):
+                yield y
+            elif isinstance(y, (list, tuple, _Record)):
+                yield from y.tensors() if isinstance(y, _Record) else self.tensors(y)
+
+
+@dataclass
+class CountedPlan(_Record):
+    """Plan from the buckets' actual counts (``_counted_plan``)."""
+    item: torch.Tensor                  # the sorted entries without the zero-digit sentinels
+    bk: np.ndarray                      # sorted ids of the non-empty buckets (host)
+    passes: list                        # segmented slices down to one value per such bucket (``_reduce``)
+    G: int
+    W: int
+    c: int
+    weights: DigitWeights | ChunkWeights | None    # None: no bucket holds an entry
+
+
+def _counted_plan(k: torch.Tensor, group, n_groups: int, W: int, c: int, weights: type,
+                  first_slice: int | None = None) -> CountedPlan:
+    """ONE host sync (the counts), any grouping; ``weights``: the record class of its weights."""
     dev = k.device
     items, first, end = _runs(k, group, n_groups, W, c)
     counts = (end - first).cpu().numpy().astype(np.int64)               # the plan's one device-to-host copy
@@ -243,33 +273,39 @@ def _counted_plan(k: torch.Tensor, group, n_groups: int, W: int, c: int, first_s
     passes = _segment_passes_dev(counts[bk], dev, first_slice)
     if bk.size and not passes:  # every bucket holds one entry
         passes = [(torch.arange(bk.size, device=dev), torch.ones(bk.size, dtype=torch.int32, device=dev))]
-    return {"item": items[: int(counts.sum())], "bk": bk, "passes": passes, "W": W, "c": c}
+    return CountedPlan(items[: int(counts.sum())], bk, passes, n_groups, W, c,
+                       weights.build(bk, c, dev) if bk.size else None)
 
 
-# A counted plan takes ONE host sync (the per-bucket counts decide the slice
-# passes).  A device-resident plan fixes its layout from the plan's SHAPE
-# instead: every bucket owns a number of lanes set by its window's expected
-# run (uniform digits: the batch weights are uniform), each lane takes an
-# equal share of the bucket's actual run (csrc/kernels/dx_plan.hip
-# dx_lane_slices), the multi-lane buckets reduce by a fixed tree and the
-# bucket weighting runs over a fixed set of buckets.  Nothing goes through the
-# host, so every pass is queued at once behind the sort.
-
-_DPLANS: dict = {}
+_DPLANS = {}       # (shape, device, weights record class) -> DeviceLayout, in the order built
 _PLAN_LIMIT = 32
 
 
-def _layout_tensors(lay: dict):
-    for k, v in lay.items():
-        if isinstance(v, torch.Tensor):
-            yield v
-        elif k == "passes":
-            for st, ln in v:
-                yield st
-                yield ln
+@dataclass
+class DeviceLayout(_Record):
+    """A counted plan takes ONE host sync (the per-bucket counts decide the
+    slice passes).  A device-resident plan fixes its layout from the plan's
+    SHAPE instead: every bucket owns a number of lanes set by its window's
+    expected run (uniform digits: the batch weights are uniform), each lane
+    takes an equal share of the bucket's actual run (csrc/kernels/dx_plan.hip
+    dx_lane_slices), the multi-lane buckets reduce by a fixed tree and the
+    bucket weighting runs over a fixed set of buckets.  Nothing goes through
+    the host, so every pass is queued at once behind the sort."""
+    n_lanes: int
+    used: np.ndarray                    # sorted ids of the buckets of the declared widths (host)
+    lane_bucket: torch.Tensor           # per lane: its bucket, and its rank among the bucket's lanes
+    lane_j: torch.Tensor
+    lanes: torch.Tensor                 # per bucket: its lane count, and its first lane
+    first_lane: torch.Tensor
+    multi: torch.Tensor                 # the buckets with several lanes
+    passes: list                        # the tree over their lanes
+    used_t: torch.Tensor
+    unused_t: torch.Tensor
+    weights: DigitWeights | ChunkWeights
+    _streams: set = field(default_factory=set)      # ids of the streams recorded on ``tensors()`` (``_mark_use``)
 
 
-def _mark_use(lay: dict, dev):
+def _mark_use(lay: DeviceLayout, dev):
     """A cached layout is read by kernels of whatever stream the caller is on;
     its tensors were allocated on the stream that built it.  Every new user
     stream is recorded on them (``record_stream``), so when the cache evicts
@@ -282,13 +318,10 @@ def _mark_use(lay: dict, dev):
     keep = getattr(_CAPTURE, "keep", None)
     if keep is not None:
         keep.append(lay)
-    if dev.type != "cuda":
-        return
-    s = torch.cuda.current_stream(dev)
-    seen = lay.setdefault("_streams", set())
-    if s.stream_id not in seen:
-        seen.add(s.stream_id)
-        for t in _layout_tensors(lay):
+    s = torch.cuda.current_stream(dev) if dev.type == "cuda" else None
+    if s is not None and s.stream_id not in lay._streams:
+        lay._streams.add(s.stream_id)
+        for t in lay.tensors():
             t.record_stream(s)
 
 
@@ -311,14 +344,14 @@ class capture_keep:
         return False
 
 
-def _device_layout(groups: tuple, W: int, c: int, sl: int, dev) -> dict:
-    """Static layout of a device-resident plan (cached per shape).
+def _device_layout(groups: tuple, W: int, c: int, sl: int, dev, weights: type | None = None) -> DeviceLayout:
+    """The layout of a shape, cached per shape and ``weights`` record class (default ``ChunkWeights``).
     ``groups`` = ((entries, scalar bits), ...) per group.  Window w of a group
     with b = min(c, bits - w c) > 0 bits uses the buckets of digits 1 .. 2^b - 1,
     each with ceil(entries / (2^b sl)) lanes; every other bucket keeps one lane
     and must stay empty (``overflow`` counts entries that land there)."""
-    dev = torch.device(dev)
-    key = (groups, W, c, sl, str(dev))
+    dev, weights = torch.device(dev), weights or ChunkWeights
+    key = (groups, W, c, sl, str(dev), weights)
     lay = _DPLANS.get(key)
     if lay is not None:
         _mark_use(lay, dev)
@@ -345,12 +378,12 @@ def _device_layout(groups: tuple, W: int, c: int, sl: int, dev) -> dict:
     passes = _segment_passes(lanes[multi], off[multi])
     up = lambda a, dt: _upload(np.asarray(a).astype(dt), dev)  # noqa: E731
     ubk = np.flatnonzero(used)
-    lay = {"nb": nb, "n_lanes": L, "W": W, "c": c, "used": ubk,
-           "lane_bucket": up(lane_bucket, np.int32), "lane_j": up(lane_j, np.int32), "lanes": up(lanes, np.int32),
-           "first_lane": up(off, np.int64), "multi": up(multi, np.int64),
-           "passes": [(up(st, np.int64), up(ln, np.int32)) for st, ln in passes],
-           "used_t": up(ubk, np.int64), "unused_t": up(np.flatnonzero(~used), np.int64)}
-    if dev.type == "cuda":  # uploaded on this stream; readers on others must not see it half-copied
+    lay = DeviceLayout(L, ubk, lane_bucket=up(lane_bucket, np.int32), lane_j=up(lane_j, np.int32),
+                       lanes=up(lanes, np.int32), first_lane=up(off, np.int64), multi=up(multi, np.int64),
+                       passes=[(up(st, np.int64), up(ln, np.int32)) for st, ln in passes],
+                       used_t=up(ubk, np.int64), unused_t=up(np.flatnonzero(~used), np.int64),
+                       weights=weights.build(ubk, c, dev))
+    if dev.type == "cuda":  # uploaded on this stream, weights included; readers on others must not see it half-copied
         torch.cuda.current_stream(dev).synchronize()
     while len(_DPLANS) > _PLAN_LIMIT:  # least recently built first (see ``_mark_use`` for why that is safe)
         _DPLANS.pop(next(iter(_DPLANS)))
@@ -359,134 +392,128 @@ def _device_layout(groups: tuple, W: int, c: int, sl: int, dev) -> dict:
     return lay
 
 
-def _lane_slices(first: torch.Tensor, end: torch.Tensor, lay: dict):
+def _lane_slices(first: torch.Tensor, end: torch.Tensor, lay: DeviceLayout):
     """Every lane's equal share of its bucket's run: the layout's first pass."""
-    L = lay["n_lanes"]
+    L = lay.n_lanes
     st = torch.empty(L, dtype=torch.int64, device=first.device)
     ln = torch.empty(L, dtype=torch.int32, device=first.device)
     g, s = _ctx(first, st)
-    _call("dx_lane_slices", g, s, _ptr(first), _ptr(end), _ptr(lay["lane_bucket"]), _ptr(lay["lane_j"]),
-          _ptr(lay["lanes"]), L, _ptr(st), _ptr(ln))
+    _call("dx_lane_slices", g, s, _ptr(first), _ptr(end), _ptr(lay.lane_bucket), _ptr(lay.lane_j),
+          _ptr(lay.lanes), L, _ptr(st), _ptr(ln))
     return st, ln
 
 
-def _reduce(passes: list, ops: tuple, lay: dict | None = None) -> torch.Tensor:
+def _reduce(passes: list, ops: tuple, lay: DeviceLayout | None = None) -> torch.Tensor:
     """Sorted entries -> one row per bucket that carries a value.  ``ops`` =
-    (first, next): passes[0] reads the source through the item index
-    (``first(start, len)``), every later pass reads the level before
-    (``next(cur, start, len)``).  A counted plan's passes end at one row per
+    (first, next): passes[0] reads the source through the item index, every
+    later pass the level before.  A counted plan's passes end at one row per
     bucket of ``bk``.  With a layout the first pass leaves one row per lane: a
     single-lane bucket's is its value, the later passes are the tree over the
-    multi-lane buckets' lanes -> one row per USED bucket (``lay["used"]`` order)."""
+    multi-lane buckets' lanes -> one row per USED bucket (``lay.used`` order)."""
     first_op, next_op = ops
     cur = first_op(*passes[0])
-    B = cur.index_select(0, lay["first_lane"]) if lay is not None else None
+    B = cur.index_select(0, lay.first_lane) if lay is not None else None
     for st, ln in passes[1:]:
-        cur = next_op(cur, st, ln)
+        cur = next_op(cur, None, st, ln)
     if lay is None:
         return cur
     if len(passes) > 1:
-        B.index_copy_(0, lay["multi"], cur)
-    return B.index_select(0, lay["used_t"])
+        B.index_copy_(0, lay.multi, cur)
+    return B.index_select(0, lay.used_t)
 
 
-def _device_buckets(k: torch.Tensor, group, groups: tuple, W: int, c: int, sl: int, ops):
-    """Runs, shape-derived layout (``sl`` entries per lane) and reduction, all
-    queued without a host sync; ``ops(items)`` gives the group's slice
-    operations -> (one row per used bucket, layout, overflow: the entries in
-    buckets outside the layout, i.e. scalars wider than declared, as a device
-    scalar for ``check_overflow``)."""
+def _device_buckets(k: torch.Tensor, group, groups: tuple, W: int, c: int, sl: int, weights: type, ops):
+    """Runs, shape-derived layout (``sl`` entries per lane, ``weights`` record)
+    and reduction, all queued without a host sync; ``ops(items)`` gives the
+    group's slice operations -> (one row per used bucket, layout, overflow:
+    the entries in buckets outside the layout, i.e. scalars wider than
+    declared, as a device scalar for ``check_overflow``)."""
     items, first, end = _runs(k, group, len(groups), W, c)
-    lay = _device_layout(tuple(groups), W, c, sl, k.device)
-    B = _reduce([_lane_slices(first, end, lay)] + lay["passes"], ops(items), lay)
-    return B, lay, (end - first).index_select(0, lay["unused_t"]).sum()
+    lay = _device_layout(tuple(groups), W, c, sl, k.device, weights)
+    B = _reduce([_lane_slices(first, end, lay)] + lay.passes, ops(items), lay)
+    return B, lay, (end - first).index_select(0, lay.unused_t).sum()
 
 
-def check_overflow(h: dict):
-    """Raise if a device-resident plan dropped entries (checked once the
-    results are read back, so it costs no extra host sync)."""
-    ov = h.get("overflow")
-    if ov is not None and int(ov) != 0:
-        raise RuntimeError(f"device bucket plan: {int(ov)} entries fell outside the declared scalar widths")
+@dataclass
+class Handle(_Record):
+    """What a launched product leaves for its finisher."""
+    G: int
+    W: int
+    c: int
+    rows: torch.Tensor | None = None    # per-window rows (G2 hands its window sums over beside the handle)
+    gws: np.ndarray | None = None       # the (group, window) g W + w of every row; None: all G W, in order
+    overflow: torch.Tensor | None = None    # a device plan's entries outside the declared widths
+    torus: bool = False                 # GT rows are numerators of torus images
+
+
+def check_overflow(h: Handle):
+    """Raise if a device-resident plan dropped entries (checked once the results are read back: no extra host sync)."""
+    if h.overflow is not None and int(h.overflow) != 0:
+        raise RuntimeError(f"device bucket plan: {int(h.overflow)} entries fell outside the declared scalar widths")
 
 
 # ----------------------------------------------------------------------------- weights
-def _g1_weight_plan(bk, dev) -> dict:
-    """Bucket weights of the sorted 8-bit-window bucket keys ``bk``: the digit
-    scalars of d * B_{g,w,d}, then per-(group, window) sums -- the keys are
-    (g W + w) 256 + d, so each (group, window) is a contiguous run."""
-    sc = np.zeros((bk.size, 8), dtype=np.int32)
-    sc[:, 0] = bk % 256
-    gws, counts = np.unique(bk // 256, return_counts=True)
-    return {"sc": _upload(sc, dev), "gws": gws,
-            "passes": [(_upload(st, dev), _upload(ln.astype("int32"), dev)) for st, ln in _segment_passes(counts)]}
+@dataclass
+class DigitWeights(_Record):
+    """G1: the digit scalars of d * B_{g,w,d}, then per-(group, window) sums -- the sorted
+    bucket keys are (g W + w) 2^c + d, so each (group, window) is a contiguous run."""
+    sc: torch.Tensor                    # [buckets, 8] digit scalars
+    gws: np.ndarray                     # the (group, window) of every summed row (host)
+    passes: list
+
+    @classmethod
+    def build(cls, bk, c: int, dev) -> DigitWeights:
+        sc = np.zeros((bk.size, 8), dtype=np.int32)
+        sc[:, 0] = bk & ((1 << c) - 1)
+        gws, counts = np.unique(bk >> c, return_counts=True)
+        return cls(_upload(sc, dev), gws,
+                   [(_upload(st, dev), _upload(ln.astype("int32"), dev)) for st, ln in _segment_passes(counts)])
+
+    def weigh(self, B: torch.Tensor) -> tuple:
+        """Bucket sums -> d * B_{g,w,d} (one short variable-base launch) ->
+        per-(group, window) sums on the device -> (one row per ``gws``, ``gws``)."""
+        cur = g1_mul(B, self.sc)
+        for st, ln in self.passes:
+            cur = g1_slice_sum(cur, None, st, ln)
+        return cur, self.gws
 
 
-def _g1_weigh(h: dict, cur: torch.Tensor, wp: dict):
-    """Bucket sums -> d * B_{g,w,d} (one short variable-base launch) ->
-    per-(group, window) sums on the device (``g1_msm_finish`` ends on the host)."""
-    cur = g1_mul(cur, wp["sc"])
-    for st, ln in wp["passes"]:
-        cur = g1_slice_sum(cur, None, st, ln)
-    h["S_w"], h["gws"] = cur, wp["gws"]
+@dataclass
+class ChunkWeights(_Record):
+    """G2 and GT: running sums / running products over chunks of an aligned
+    digit range (csrc/kernels/dx_rpmsm.hip chunk_weight_one, dx_range.hip
+    gt_chunk_weight_coop), then per-(group, window) sums of the chunk results."""
+    d: torch.Tensor                     # every bucket's digit
+    chunks: tuple                       # (first bucket, buckets, digit base) of every chunk
+    gws: torch.Tensor                   # the (group, window) of every summed row
+    passes: list
 
+    @classmethod
+    def build(cls, bk, c: int, dev) -> ChunkWeights:
+        # digit range of a chunk: 32 (about two additions per bucket) while that still gives ~16k chunk lanes,
+        # shorter for a small plan (a 1/8 pool slice: 8, i.e. 4x the lanes with a third of the chain)
+        chunk = G2_CHUNK
+        while chunk > 4 and bk.size // chunk < 16384:
+            chunk //= 2
+        dig = bk & ((1 << c) - 1)
+        gw = bk >> c
+        ck = gw * ((1 << c) // chunk + 1) + dig // chunk
+        first = np.flatnonzero(np.r_[True, ck[1:] != ck[:-1]])
+        clen = np.diff(np.r_[first, bk.size])
+        gwf = gw[first]                                  # sorted: run lengths instead of np.unique's sort
+        gstart = np.flatnonzero(np.r_[True, gwf[1:] != gwf[:-1]])
+        gws, gcounts = gwf[gstart], np.diff(np.r_[gstart, gwf.size])
+        return cls(_upload(dig.astype("int32"), dev),
+                   (_upload(first.astype(np.int64), dev), _upload(clen.astype(np.int32), dev),
+                    _upload(((dig[first] // chunk) * chunk).astype(np.int32), dev)),
+                   _upload(gws.astype(np.int64), dev), _segment_passes_dev(gcounts, dev))
 
-def _g2_chunk(n_buckets: int) -> int:
-    """Digit range of a bucket-weight chunk: 32 (about two additions per
-    bucket) while that still gives ~16k chunk lanes, shorter for a small
-    plan (a 1/8 pool slice: 8, i.e. 4x the lanes with a third of the chain)."""
-    ch = G2_CHUNK
-    while ch > 4 and n_buckets // ch < 16384:
-        ch //= 2
-    return ch
-
-
-def _chunk_weight_plan(bk, c: int, dev) -> dict:
-    """Bucket weights by running sums (G2) / running products (GT) over
-    chunks of an aligned digit range (csrc/kernels/dx_rpmsm.hip
-    chunk_weight_one, dx_range.hip gt_chunk_weight_coop), then per-window
-    sums of the chunk results, for the sorted bucket keys ``bk``."""
-    chunk = _g2_chunk(bk.size)
-    dig = bk & ((1 << c) - 1)
-    gw = bk >> c
-    ck = gw * ((1 << c) // chunk + 1) + dig // chunk
-    first = np.flatnonzero(np.r_[True, ck[1:] != ck[:-1]])
-    clen = np.diff(np.r_[first, bk.size])
-    gwf = gw[first]                                  # sorted: run lengths instead of np.unique's sort
-    gstart = np.flatnonzero(np.r_[True, gwf[1:] != gwf[:-1]])
-    gws, gcounts = gwf[gstart], np.diff(np.r_[gstart, gwf.size])
-    return {"d": _upload(dig.astype("int32"), dev),
-            "chunks": (_upload(first.astype(np.int64), dev), _upload(clen.astype(np.int32), dev),
-                       _upload(((dig[first] // chunk) * chunk).astype(np.int32), dev)),
-            "gws": _upload(gws.astype(np.int64), dev), "gpasses": _segment_passes_dev(gcounts, dev)}
-
-
-def _g2_weigh(cur, wp: dict, S: torch.Tensor) -> torch.Tensor:
-    cur = g2_chunk_weight(cur, wp["d"], *wp["chunks"])
-    for st, ln in wp["gpasses"]:
-        cur = g2_slice_sum(cur, None, st, ln, False)
-    S.index_copy_(0, wp["gws"], cur)
-    return S
-
-
-def _me_windows(h: dict, cur, bk, n_groups: int, W: int, c: int, dev):
-    """Bucket values -> B^d (GPU) scattered into per-(group, window) rows,
-    reduced on the device down to <= 32 rows each (``multi_exp_grouped_finish``
-    ends on the host)."""
-    digit_sc = torch.zeros((bk.size, 8), dtype=torch.int32)
-    digit_sc[:, 0] = torch.from_numpy((bk & ((1 << c) - 1)).astype("int32"))
-    bkp = gt_pow(cur, _upload(digit_sc.numpy(), dev))
-    D = 1 << c
-    g, w, d = bk // (W * D), (bk >> c) % W, bk & (D - 1)
-    slot = _upload(d * (n_groups * W) + g * W + w, dev)
-    win = gt_one(dev).repeat(D * n_groups * W, 1)
-    win[slot] = bkp
-    win = win.view(D, n_groups * W, 96)
-    if torch.device(dev).type == "cuda":  # 8-way device levels down to <= 32 rows per (group, window)
-        while win.shape[0] > 32:
-            win = _gt_prod_level(win, 8)
-    h["win"] = win
-    h["G"] = n_groups
+    def weigh(self, B: torch.Tensor, chunk_op, slice_op, out: torch.Tensor) -> torch.Tensor:
+        """One row per bucket -> ``out`` [G W, .] (neutral rows) with the row of every window that holds a bucket."""
+        cur = chunk_op(B, self.d, *self.chunks)
+        for st, ln in self.passes:
+            cur = slice_op(cur, None, st, ln)
+        return out.index_copy_(0, self.gws, cur)
 
 
 # ----------------------------------------------------------------------------- GT multi-exponentiation
@@ -504,11 +531,16 @@ def me_window(groups: tuple, lo: int = 8, hi: int = 16) -> tuple:
 
 def multi_exp_plan(k: torch.Tensor, group, n_groups: int, W: int = 8, c: int = 8):
     """The bucket plan of ``multi_exp_grouped`` alone (its one host sync)."""
-    return _counted_plan(k, group, n_groups, W, c)
+    return _counted_plan(k, group, n_groups, W, c, ChunkWeights)
+
+
+def _gt_windows(B: torch.Tensor, wp: ChunkWeights, G: int, W: int) -> torch.Tensor:
+    """One row per bucket -> the dense [1, G W, 96] window rows; a window without a bucket is one."""
+    return wp.weigh(B, gt_chunk_weight, gt_slice_prod, gt_one(B.device).repeat(G * W, 1)).view(1, G * W, 96)
 
 
 def multi_exp_grouped(a: torch.Tensor, k: torch.Tensor, group, n_groups: int, W: int = 8, c: int = 8,
-                      plan: dict | None = None):
+                      plan: CountedPlan | None = None) -> Handle:
     """Launch G independent multi-exponentiations prod_{i: group_i = g} a[i % n]^k_i
     (n = rows of a, k [m, 8] with m a multiple of n, low W c-bit windows of
     each exponent; ``group`` an int32 tensor or an int stride) as ONE bucket
@@ -516,17 +548,15 @@ def multi_exp_grouped(a: torch.Tensor, k: torch.Tensor, group, n_groups: int, W:
     verifying nodes, unless ``plan`` comes from ``multi_exp_plan``).  Returns a
     handle for ``multi_exp_grouped_finish``; device passes are queued on the
     current stream."""
-    if plan is None:
-        plan = _counted_plan(k, group, n_groups, W, c)
-    h = {"G": n_groups, "W": W, "c": c, "win": None}
-    if plan["bk"].size:
-        cur = _reduce(plan["passes"], _gt_ops(a, plan["item"]))
-        _me_windows(h, cur, plan["bk"], n_groups, W, c, a.device)
+    plan = plan or multi_exp_plan(k, group, n_groups, W, c)
+    h = Handle(n_groups, W, c)
+    if plan.weights is not None:
+        h.rows = _gt_windows(_reduce(plan.passes, _gt_ops(a, plan.item)), plan.weights, n_groups, W)
     return h
 
 
 def multi_exp_device(a: torch.Tensor, k: torch.Tensor, group, groups: tuple, W: int | None = None,
-                     c: int | None = None, item_split: tuple | None = None, first_slice: int | None = None) -> dict:
+                     c: int | None = None, item_split: tuple | None = None, first_slice: int | None = None) -> Handle:
     """``multi_exp_grouped`` with a device-resident plan (no host sync):
     ``groups`` = ((entries, exponent bits), ...) per group (window from
     ``me_window`` unless given).  -> the handle of ``multi_exp_grouped_finish``.
@@ -537,35 +567,27 @@ def multi_exp_device(a: torch.Tensor, k: torch.Tensor, group, groups: tuple, W: 
     entries per lane, default ``_ME_TORUS_SLICE``), the later passes are
     unchanged, and ``multi_exp_grouped_finish`` maps the per-window rows back
     by ``gt_pi``: the same results, bit for bit."""
-    dev = a.device
     torus = a.shape[-1] == 48
     sl = first_slice or (_ME_TORUS_SLICE if torus else _ME_SLICE)
     G = len(groups)
     if c is None:
         W, c = me_window(tuple(groups))
-    B, lay, overflow = _device_buckets(k, group, groups, W, c, sl, lambda items: _gt_ops(a, items, item_split))
-    if "gtw" not in lay:
-        lay["gtw"] = _chunk_weight_plan(lay["used"], c, dev)
-    wp = lay["gtw"]
-    cur = gt_chunk_weight(B, wp["d"], *wp["chunks"])                     # running products per chunk
-    for st, ln in wp["gpasses"]:
-        cur = gt_slice_prod(cur, None, st, ln)                            # chunks -> (group, window)
-    win = gt_one(dev).repeat(G * W, 1)
-    win.index_copy_(0, wp["gws"], cur)
-    return {"G": G, "W": W, "c": c, "win": win.view(1, G * W, 96), "overflow": overflow, "torus": torus}
+    B, lay, overflow = _device_buckets(k, group, groups, W, c, sl, ChunkWeights,
+                                       lambda items: _gt_ops(a, items, item_split))
+    return Handle(G, W, c, _gt_windows(B, lay.weights, G, W), overflow=overflow, torus=torus)
 
 
-def multi_exp_grouped_finish(h) -> torch.Tensor:
-    """[G, 96] host results: per-window products and the Horner steps on the host."""
-    G, W = h["G"], h["W"]
-    if h["win"] is None:
+def multi_exp_grouped_finish(h: Handle) -> torch.Tensor:
+    """[G, 96] host results: the Horner steps over the window rows on the host."""
+    G, W = h.G, h.W
+    if h.rows is None:
         return gt_one("cpu").repeat(G, 1)
-    S_w = gt_prod(h["win"].cpu(), chunk=64)                 # host: one chain per (group, window)
-    if h.get("torus"):                                      # numerators -> the canonical unitary values
+    S_w = gt_prod(h.rows.cpu(), chunk=64)                   # [1, G W, 96] -> [G W, 96]
+    if h.torus:                                             # numerators -> the canonical unitary values
         S_w = gt_pi(S_w)
     S_w = S_w.view(G, W, 96)
     acc = S_w[:, W - 1].contiguous()
-    sh = _pow2_scalar(h["c"]).expand(G, 8).contiguous()
+    sh = _pow2_scalar(h.c).expand(G, 8).contiguous()
     for w in range(W - 2, -1, -1):
         acc = gt_mul(gt_pow(acc, sh), S_w[:, w].contiguous())
     return acc
@@ -595,53 +617,39 @@ def g1_msm_grouped(P_jac: torch.Tensor, k: torch.Tensor, group: torch.Tensor | N
 def g1_msm_plan(k: torch.Tensor, group, n_groups: int, bits: int = 256):
     """The bucket plan of ``g1_msm_launch`` alone (its one host sync), so a
     caller can take every plan's sync before queueing any heavy pass."""
-    if not k.shape[0]:
-        return None
-    return _counted_plan(k, group, n_groups, (bits + 7) // 8, 8)
+    return _counted_plan(k, group, n_groups, (bits + 7) // 8, 8, DigitWeights) if k.shape[0] else None
 
 
 def g1_msm_launch(P_jac: torch.Tensor, k: torch.Tensor, group: torch.Tensor | None, n_groups: int,
-                  bits: int = 256, plan: dict | None = None) -> dict:
+                  bits: int = 256, plan: CountedPlan | None = None) -> Handle:
     """First half of g1_msm_grouped: the bucket plan (one host sync on k,
     unless ``plan`` comes from ``g1_msm_plan``) and every device pass, queued
     on the current stream.  g1_msm_finish waits for them and runs the Horner
     steps on the host."""
     assert P_jac.shape[0] == k.shape[0]
     assert group is None or isinstance(group, int) or group.numel() == k.shape[0]
-    W = (bits + 7) // 8
-    h = {"n_groups": n_groups, "W": W, "S_w": None}
-    if P_jac.shape[0] == 0:
-        return h
-    if plan is None:
-        plan = _counted_plan(k, group, n_groups, W, 8)
-    bk = plan["bk"]
-    if bk.size:
-        cur = _reduce(plan["passes"], _g1_ops(P_jac, plan["item"]))
-        _g1_weigh(h, cur, _g1_weight_plan(bk, P_jac.device))
-    return h
+    plan = plan or g1_msm_plan(k, group, n_groups, bits)
+    if plan is None or plan.weights is None:
+        return Handle(n_groups, (bits + 7) // 8, 8)
+    return Handle(n_groups, plan.W, 8, *plan.weights.weigh(_reduce(plan.passes, _g1_ops(P_jac, plan.item))))
 
 
-def g1_msm_device(P_jac: torch.Tensor, k: torch.Tensor, group, groups: tuple, bits: int = 256) -> dict:
+def g1_msm_device(P_jac: torch.Tensor, k: torch.Tensor, group, groups: tuple, bits: int = 256) -> Handle:
     """``g1_msm_launch`` with a device-resident plan (8-bit windows, no host
     sync) -> the handle of ``g1_msm_finish``."""
     W = (bits + 7) // 8
-    B, lay, overflow = _device_buckets(k, group, groups, W, 8, _ME_SLICE, lambda items: _g1_ops(P_jac, items))
-    h = {"n_groups": len(groups), "W": W, "S_w": None, "overflow": overflow}
-    if "g1w" not in lay:
-        lay["g1w"] = _g1_weight_plan(lay["used"], P_jac.device)
-    _g1_weigh(h, B, lay["g1w"])
-    return h
+    B, lay, overflow = _device_buckets(k, group, groups, W, 8, _ME_SLICE, DigitWeights,
+                                       lambda items: _g1_ops(P_jac, items))
+    return Handle(len(groups), W, 8, *lay.weights.weigh(B), overflow)
 
 
-def g1_msm_finish(h: dict) -> torch.Tensor:
+def g1_msm_finish(h: Handle) -> torch.Tensor:
     from ..crypto.bn254 import g1_infinity_jac
 
-    out = g1_infinity_jac(h["n_groups"], "cpu")
-    if h["S_w"] is None:
-        return out
-    W, gws = h["W"], h["gws"]
-    S_w = h["S_w"].cpu()                                                 # [len(gws), 24]
-    G = h["n_groups"]
+    G, W, gws = h.G, h.W, h.gws
+    if h.rows is None:
+        return g1_infinity_jac(G, "cpu")
+    S_w = h.rows.cpu()                                                   # [len(gws), 24]
     # Horner over the windows, all groups at once: acc = 2^8 acc + S_{g,w}.
     # ~8 doublings per window and group, instead of one up-to-248-doubling
     # multiplication 2^{8w} S_{g,w} per (group, window)
@@ -660,28 +668,24 @@ def g1_msm_finish(h: dict) -> torch.Tensor:
 # ----------------------------------------------------------------------------- G2 MSM (verifier mode "msm")
 # csrc/kernels/dx_rpmsm.hip: range-proof batch verification by bilinearity
 def g2_msm_launch(P_aff: torch.Tensor, k: torch.Tensor, group: torch.Tensor | None, n_groups: int,
-                  c: int = 13, bits: int = 254, first_slice: int = 32):
+                  c: int = 13, bits: int = 254, first_slice: int = 32) -> CountedPlan:
     """Bucket plan of G independent G2 MSMs out[g] = sum_{t: group_t = g}
     k_t P[t % m] (m = rows of P_aff, k [n, 8] with n a multiple of m; group:
     int32 tensor, or an int stride s meaning group_t = t // s) over c-bit
     windows, with its bucket weights -- ONE host sync (the counts).
     ``g2_msm_run`` queues the device passes."""
-    m = _rows(P_aff, 32)
-    assert k.shape[0] % m == 0
-    h = _counted_plan(k, group, n_groups, -(-bits // c), c, first_slice)
-    h.update(G=n_groups, m=m)
-    if h["bk"].size:
-        h.update(_chunk_weight_plan(h["bk"], c, P_aff.device))
-    return h
+    assert k.shape[0] % _rows(P_aff, 32) == 0
+    return _counted_plan(k, group, n_groups, -(-bits // c), c, ChunkWeights, first_slice)
 
 
-def g2_msm_run(P_aff: torch.Tensor, h: dict) -> torch.Tensor:
+def g2_msm_run(P_aff: torch.Tensor, h: CountedPlan) -> torch.Tensor:
     """Device passes of a ``g2_msm_launch`` plan, queued on the current stream:
     bucket sums, weights d B_d, per-(group, window) sums -> [G * W, 48]
     Jacobian window sums (``g2_msm_finish`` combines them)."""
-    S = torch.zeros((h["G"] * h["W"], 48), dtype=torch.int32, device=P_aff.device)   # Jacobian infinity = Z 0
-    if h["bk"].size:
-        _g2_weigh(_reduce(h["passes"], _g2_ops(P_aff, h["item"], h["m"])), h, S)
+    S = torch.zeros((h.G * h.W, 48), dtype=torch.int32, device=P_aff.device)     # Jacobian infinity = Z 0
+    if h.weights is not None:
+        B = _reduce(h.passes, _g2_ops(P_aff, h.item, _rows(P_aff, 32)))
+        h.weights.weigh(B, g2_chunk_weight, _g2_jac_sum, S)
     return S
 
 
@@ -690,24 +694,20 @@ def g2_msm_device(P_aff: torch.Tensor, k: torch.Tensor, group, groups: tuple, c:
     """``g2_msm_launch`` + ``g2_msm_run`` with a device-resident plan (no host
     sync): out[g] = sum_{t: group_t = g} k_t P[t % m] -> ([G * W, 48] window
     sums, handle for ``g2_msm_finish``)."""
-    dev = P_aff.device
-    m = _rows(P_aff, 32)
     G = len(groups)
     W = -(-bits // c)
-    B, lay, overflow = _device_buckets(k, group, groups, W, c, 32, lambda items: _g2_ops(P_aff, items, m))
-    if "g2w" not in lay:
-        lay["g2w"] = _chunk_weight_plan(lay["used"], c, dev)
-    S = torch.zeros((G * W, 48), dtype=torch.int32, device=dev)
-    _g2_weigh(B, lay["g2w"], S)
-    return S, {"G": G, "W": W, "c": c, "overflow": overflow}
+    B, lay, overflow = _device_buckets(k, group, groups, W, c, 32, ChunkWeights,
+                                       lambda items: _g2_ops(P_aff, items, _rows(P_aff, 32)))
+    S = torch.zeros((G * W, 48), dtype=torch.int32, device=P_aff.device)
+    return lay.weights.weigh(B, g2_chunk_weight, _g2_jac_sum, S), Handle(G, W, c, overflow=overflow)
 
 
-def g2_msm_finish(S: torch.Tensor, h: dict, out_aff: torch.Tensor | None = None, stride: int = 1,
+def g2_msm_finish(S: torch.Tensor, h: CountedPlan | Handle, out_aff: torch.Tensor | None = None, stride: int = 1,
                   offset: int = 0) -> torch.Tensor:
     """Horner over the windows, one lane per group (W*c doublings), on the
     tensor's device: out_aff[g * stride + offset] = affine(out[g]).  On the
     host (CPU tensors) a core runs this serial chain ~5x faster than one GPU lane."""
-    G, W, c = h["G"], h["W"], h["c"]
+    G, W, c = h.G, h.W, h.c
     if out_aff is None:
         out_aff = torch.zeros((G, 32), dtype=torch.int32, device=S.device)
     g, s = _ctx(S, out_aff)

@@ -343,7 +343,7 @@ def test_layout_cache_serves_second_call(device, kind, g1_pool, g2_pool, gt_pool
     n, W, c, bits, fs, s = (GT_SHAPE[x] for x in ("n", "W", "c", "bits", "first_slice", "s"))
     if kind == "g2":
         m, c2, b2, s2 = (G2_SHAPE[x] for x in ("m", "c", "bits", "s"))
-        key, wkey = (((m, b2),) * 3, -(-b2 // c2), c2, 32), "g2w"
+        key, wkey = (((m, b2),) * 3, -(-b2 // c2), c2, 32), msm.ChunkWeights
 
         def run(vkind, mm=m, cc=c2):
             idx, ks = _scalars_for(vkind, 3, mm, b2, s2, rnd)
@@ -352,7 +352,7 @@ def test_layout_cache_serves_second_call(device, kind, g1_pool, g2_pool, gt_pool
 
         first, between, second = (lambda: run("halves")), (lambda: run("random", 26, 3)), (lambda: run("random"))
     elif kind == "g1":
-        key, wkey = (((n, 2),) * len(SCENARIOS), 1, 8, msm._ME_SLICE), "g1w"
+        key, wkey = (((n, 2),) * len(SCENARIOS), 1, 8, msm._ME_SLICE), msm.DigitWeights
 
         def run(order, b=2, sb=3):
             idx, ks = _group_inputs(n, b, sb, rnd, order)
@@ -360,7 +360,7 @@ def test_layout_cache_serves_second_call(device, kind, g1_pool, g2_pool, gt_pool
 
         first, between, second = (lambda: run(SCENARIOS)), (lambda: run(SCENARIOS, 10, 0x2a5)), (lambda: run(order2))
     elif kind == "gt":
-        key, wkey = (((n, bits),) * len(SCENARIOS), W, c, fs), "gtw"
+        key, wkey = (((n, bits),) * len(SCENARIOS), W, c, fs), msm.ChunkWeights
 
         def run(order, nn=n):
             idx, ks = _group_inputs(nn, bits, s, rnd, order)
@@ -369,7 +369,7 @@ def test_layout_cache_serves_second_call(device, kind, g1_pool, g2_pool, gt_pool
 
         first, between, second = (lambda: run(SCENARIOS)), (lambda: run(SCENARIOS[:3], 34)), (lambda: run(order2))
     else:
-        key, wkey = (((2 * n, bits),) * len(SCENARIOS), W, c, fs), "gtw"
+        key, wkey = (((2 * n, bits),) * len(SCENARIOS), W, c, fs), msm.ChunkWeights
 
         def run(order, nn=n):
             idx, k_lo = _group_inputs(nn, bits, s, rnd, order)
@@ -378,14 +378,14 @@ def test_layout_cache_serves_second_call(device, kind, g1_pool, g2_pool, gt_pool
                       _gt_torus_logs(gt_pool, idx, k_lo, k_hi), order[0])
 
         first, between, second = (lambda: run(SCENARIOS)), (lambda: run(SCENARIOS[:3], 34)), (lambda: run(order2))
-    key = key + (str(_tensor_device(dev)),)
+    key = key + (str(_tensor_device(dev)), wkey)
     first()
     lay = msm._DPLANS[key]
-    assert wkey in lay
-    wp = lay[wkey]
+    wp = lay.weights
+    assert isinstance(wp, wkey)
     between()
     second()
-    assert msm._DPLANS[key] is lay and lay[wkey] is wp
+    assert msm._DPLANS[key] is lay and lay.weights is wp
 
 
 # ----------------------------------------------------------------------------- B. weights and Horner
@@ -426,6 +426,33 @@ def test_g1_weights_and_horner_edges(device, bits, g1_pool):
     for g, (k, mult) in enumerate(B_CASES_G1):
         assert g1_pool.log(B_ROWS, k) == mult * g1_pool.logs[Q] % O.R
         assert got[g] == _g1_of(mult * g1_pool.logs[Q]), g
+
+
+@pytest.mark.parametrize("device", DEVICES)
+@pytest.mark.parametrize("bits", [8, 16])
+@pytest.mark.parametrize("path", ["counted", "device", "device_torus"])
+def test_gt_weights_and_horner_edges(device, bits, path, gt_pool):
+    """The rows and exponents of the G2 cases, c = 4, five groups of four
+    entries, through the counted plan, the device plan on Fp12 rows and the
+    device plan on the rows' torus images: a chunk product that passes through
+    one, windows that are all empty (bits = 16: two more on top) and a group
+    with no entry."""
+    dev = _dev(device)
+    c, W, G = 4, bits // 4, len(B_CASES_G2)
+    a = gt_pool.take(B_ROWS * G, dev)
+    k = _k([x for ks, _ in B_CASES_G2 for x in ks], dev)
+    if path == "counted":
+        h = nt.multi_exp_grouped(a, k, 4, G, W, c)
+    else:
+        if path == "device_torus":
+            a = nt.gt_beta_rows(a)[: 4 * G]                    # the images of the rows themselves, not of frob^8
+        h = nt.multi_exp_device(a, k, 4, ((4, bits),) * G, W, c)
+    assert h.torus == (path == "device_torus")
+    got = nt.multi_exp_grouped_finish(h)
+    nt.check_overflow(h)
+    for ks, mult in B_CASES_G2:
+        assert gt_pool.log(B_ROWS, ks) == mult * gt_pool.logs[Q] % O.R                # the table above is right
+    _gt_check(got, gt_pool, [mult * gt_pool.logs[Q] for _, mult in B_CASES_G2], (path, bits))
 
 
 # ----------------------------------------------------------------------------- C. digits at the word and width edges

@@ -4,8 +4,11 @@ Round 5 captured the pool verifier's passes in HIP graphs and saw replays
 fault (profiles/r6/graph_fault.md): the plan cache evicts layouts (32 shapes)
 while a captured graph -- or, eagerly, another stream's queued kernels --
 still read them, and the caching allocator handed the freed blocks to new
-allocations.  Now every stream that reads a layout is recorded on its tensors
-(eviction waits for them) and a capture keeps every layout it reads."""
+allocations.  Now every stream that reads a layout is recorded on its tensors,
+those of its weights record included (eviction waits for them), and a capture
+keeps every layout it reads."""
+import dataclasses
+
 import pytest
 import torch
 
@@ -15,6 +18,38 @@ from drynx_amd.native import msm
 
 def _shape(i):
     return ((64 + i, 64),)
+
+
+WEIGHTS = (msm.DigitWeights, msm.ChunkWeights)
+
+
+def _walk(x):
+    """Every tensor under a record, found generically: dataclass fields,
+    lists, tuples and nested records."""
+    if isinstance(x, torch.Tensor):
+        yield x
+    elif isinstance(x, (list, tuple)):
+        for y in x:
+            yield from _walk(y)
+    elif dataclasses.is_dataclass(x):
+        for f in dataclasses.fields(x):
+            yield from _walk(getattr(x, f.name))
+
+
+def _weight_tensors(wp):
+    named = [wp.sc] if isinstance(wp, msm.DigitWeights) else [wp.d, *wp.chunks, wp.gws]
+    return named + [t for pair in wp.passes for t in pair]
+
+
+@pytest.mark.parametrize("weights", WEIGHTS)
+def test_layout_tensors_reach_every_tensor(weights):
+    """What ``_mark_use`` records streams on is everything the layout holds: a
+    tensor added to a record later and left out of ``tensors`` fails here."""
+    lay = msm._device_layout(((64, 64),), 8, 8, 32, "cpu", weights)
+    own = {t.data_ptr() for t in lay.tensors()}
+    assert own == {t.data_ptr() for t in _walk(lay)}
+    wts = {t.data_ptr() for t in _weight_tensors(lay.weights)}
+    assert len(wts) >= (1 if weights is msm.DigitWeights else 5) and wts <= own
 
 
 def test_capture_keep_collects_layouts():
@@ -32,7 +67,7 @@ def test_eviction_keeps_captured_layouts_alive(monkeypatch):
         held = msm._device_layout(_shape(10), 8, 8, 32, "cpu")
     for i in range(11, 20):  # evicts shape 10 from the cache
         msm._device_layout(_shape(i), 8, 8, 32, "cpu")
-    key = (_shape(10), 8, 8, 32, "cpu")
+    key = (_shape(10), 8, 8, 32, "cpu", msm.ChunkWeights)
     assert key not in msm._DPLANS and ck.items[0] is held
     assert held["lane_bucket"].numel() == held["n_lanes"]  # still a live tensor the graph can read
 
@@ -45,6 +80,31 @@ def test_layout_records_every_user_stream(gpu_device):
     with torch.cuda.stream(s2):
         again = msm._device_layout(_shape(40), 8, 8, 32, gpu_device)
     assert again is lay and {s1.stream_id, s2.stream_id} <= lay["_streams"]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("weights", WEIGHTS)
+def test_second_stream_is_recorded_on_every_layout_tensor(gpu_device, monkeypatch, weights):
+    """A stream that fetches a cached layout is recorded on every tensor its
+    kernels may read, the weights' tensors included."""
+    calls = []
+    record_stream = torch.Tensor.record_stream
+
+    def recorder(t, stream):
+        calls.append((t, stream.stream_id))
+        return record_stream(t, stream)
+
+    monkeypatch.setattr(torch.Tensor, "record_stream", recorder)
+    s1, s2 = torch.cuda.Stream(gpu_device), torch.cuda.Stream(gpu_device)
+    with torch.cuda.stream(s1):
+        lay = msm._device_layout(((64, 64),), 8, 8, 32, gpu_device, weights)
+    with torch.cuda.stream(s2):
+        again = msm._device_layout(((64, 64),), 8, 8, 32, gpu_device, weights)
+    assert again is lay and {s1.stream_id, s2.stream_id} <= lay._streams
+    on_s2 = {id(t) for t, sid in calls if sid == s2.stream_id}
+    walked = list(_walk(lay))
+    assert len(walked) >= 8 and all(id(t) in on_s2 for t in walked)
+    assert all(id(t) in on_s2 for t in _weight_tensors(lay.weights))
 
 
 @pytest.mark.gpu
