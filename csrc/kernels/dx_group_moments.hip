@@ -195,29 +195,64 @@ extern "C" int dx_group_moments_max_cells() { return kMaxCells; }
 // zeroed by the caller before the first window; this call adds the groups
 // [g0, g0 + gw).  Every count, cardinality, column index and the cell cap is
 // checked here: an argument that does not fit returns -2 and launches nothing.
-extern "C" int dx_group_moments(int on_gpu, void *stream, const int64_t *Z, int64_t ldz, int C, const int64_t *K,
-                                int64_t ldk, int CK, const int64_t *tiles, int64_t n_tiles, const int16_t *pairs,
-                                int P, const int64_t *keys, int n_keys, const int64_t *filters, int n_filters,
-                                int64_t g0, int64_t gw, int64_t *out) {
-  if (C < 0 || C > kMaxCols || P <= 0 || P > kMaxPairs || n_tiles < 0 || n_tiles > 0x7fffffff) return -2;
-  if (n_keys < 0 || n_keys > kMaxKeys || n_filters < 0 || n_filters > kMaxFilters || CK < 0) return -2;
-  GroupArgs a{};
+namespace {
+// The key and filter terms of a call into a: false if a count, a column index
+// or a cardinality does not fit (nothing of a is then to be used).
+bool set_terms(GroupArgs &a, int CK, const int64_t *keys, int n_keys, const int64_t *filters, int n_filters) {
+  if (n_keys < 0 || n_keys > kMaxKeys || n_filters < 0 || n_filters > kMaxFilters || CK < 0) return false;
   int64_t G = 1;
   for (int j = 0; j < n_keys; j++) {
     const int64_t col = keys[3 * j], card = keys[3 * j + 2];
-    if (col < 0 || col >= CK || card < 1 || card > kMaxGroups) return -2;
+    if (col < 0 || col >= CK || card < 1 || card > kMaxGroups) return false;
     G *= card;
-    if (G > kMaxGroups) return -2;
+    if (G > kMaxGroups) return false;
     a.kcol[j] = (int)col;
     a.koff[j] = keys[3 * j + 1];
     a.kcard[j] = card;
   }
   for (int f = 0; f < n_filters; f++) {
     const int64_t col = filters[2 * f];
-    if (col < 0 || col >= CK) return -2;
+    if (col < 0 || col >= CK) return false;
     a.fcol[f] = (int)col;
     a.fval[f] = filters[2 * f + 1];
   }
+  a.n_keys = n_keys, a.n_filters = n_filters, a.G = G;
+  return true;
+}
+
+// cell[i] = the group of row i among all G, G for a row that is dropped
+struct RowCells {
+  GroupArgs a;  // g0 = 0, gw = G: the window is every group
+  int64_t *cell;
+  __host__ __device__ void operator()(int64_t i) const {
+    const int g = row_group(a, a.K + i * a.ldk);
+    cell[i] = g < 0 ? a.G : (int64_t)g;
+  }
+};
+}  // namespace
+
+// The cell plan of a grouped encoder over other records than K14's (the
+// logistic-regression cohorts): cell[i] = the group of row i of K [rows][CK] by
+// the membership rule above (row_group, the very function of the moments), G =
+// the product of the cardinalities for a row that a filter term or an
+// out-of-range key digit drops.  keys and filters as below.
+extern "C" int dx_group_cells(int on_gpu, void *stream, const int64_t *K, int64_t ldk, int CK, int64_t rows,
+                              const int64_t *keys, int n_keys, const int64_t *filters, int n_filters,
+                              int64_t *cell) {
+  RowCells op{};
+  if (rows < 0 || !set_terms(op.a, CK, keys, n_keys, filters, n_filters)) return -2;
+  op.a.K = K, op.a.ldk = ldk, op.a.g0 = 0, op.a.gw = (int)op.a.G, op.cell = cell;
+  return dx::run(on_gpu, stream, rows, op, false, "group_cells");
+}
+
+extern "C" int dx_group_moments(int on_gpu, void *stream, const int64_t *Z, int64_t ldz, int C, const int64_t *K,
+                                int64_t ldk, int CK, const int64_t *tiles, int64_t n_tiles, const int16_t *pairs,
+                                int P, const int64_t *keys, int n_keys, const int64_t *filters, int n_filters,
+                                int64_t g0, int64_t gw, int64_t *out) {
+  if (C < 0 || C > kMaxCols || P <= 0 || P > kMaxPairs || n_tiles < 0 || n_tiles > 0x7fffffff) return -2;
+  GroupArgs a{};
+  if (!set_terms(a, CK, keys, n_keys, filters, n_filters)) return -2;
+  const int64_t G = a.G;
   if (g0 < 0 || gw < 1 || g0 + gw > G || gw * P > kMaxCells) return -2;
   if (n_tiles == 0) return 0;
   a.Z = Z, a.ldz = ldz, a.C = C, a.K = K, a.ldk = ldk, a.tiles = tiles, a.pairs = pairs, a.P = P;

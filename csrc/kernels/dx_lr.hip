@@ -44,6 +44,15 @@
 // accumulates level 1 of target t, g_t = 2 Y[i][t] - 1, in row D + t: in the
 // spare rows of the one 48-row tile-block while D + T <= 48, in further row
 // tiles beyond.  The single-label instantiations are untouched by it.
+//
+// Cohorts (a query with SQL WHERE / GROUP BY): every coefficient sum is taken
+// per cell of a DP's records.  dx_lr_encode_cells launches the same tile-block
+// plan with the grouped instantiations (a trailing LrCells argument): a block
+// reads its cell's rows through a row permutation grouped by cell (made from
+// dx_group_cells' ids by a stable sort), the cells of a window are one more
+// factor of the record-block grid dimension, and the partials [cells, record
+// blocks, P, P] are finished by dx_lr_reduce / dx_lr_reduce_pack with the
+// cells as items.  The ungrouped instantiations are untouched by it.
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <cstdio>
@@ -83,14 +92,35 @@ struct LrGrid {
   int P;  // padded output width (row stride of a partial)
 };
 
+// The grouped encoder (kCells kernels): the records of cell c0 + c are rows
+// perm[cell_start[c0 + c] .. cell_start[c0 + c + 1]) of X, y and Y.  Block x of
+// a launch is record block x % nbc of cell x / nbc.
+struct LrCells {
+  const int64_t *perm;        // [kept rows] row indices grouped by cell, record order kept inside a cell
+  const int64_t *cell_start;  // [G + 1]
+  int64_t c0;                 // first cell of the launch's window
+  int nbc;                    // record blocks per cell
+};
+
 // kDiag: every tile-block of the launch is on the diagonal (the single 3x3
 // tile-block of a narrow input): no B-side state at all.
 // kMulti: T label columns (p.Y) instead of one (p.y): the A operand of row
 // D + t is g_t = 2 Y[i][t] - 1, every other row is xa * wb.  The B operand,
 // the K-step order, the record striding and the reductions are those of the
 // single-label kernel, so each output element is the same bits as there.
-template <int TA, int TB, bool kDiag, bool kMulti = false>
-__global__ void __launch_bounds__(256) lr_encode_kernel(LrArgs p, double *__restrict__ partial, LrGrid g) {
+// kCells: the block works on one cell's records, read through the row
+// permutation (a K-step's four lanes-of-16 read four gathered rows, each still
+// one contiguous read); it strides over that cell's K-steps only, a ragged
+// last K-step contributes zero operands, and a block without a K-step writes
+// zeros.  One cell that holds every record in order is the ungrouped kernel
+// step for step.
+// The grouped kernels are the instantiations with one trailing LrCells
+// argument (Cells = LrCells); without it (the empty pack) the kernel, its
+// signature included, is the ungrouped one.
+template <int TA, int TB, bool kDiag, bool kMulti = false, class... Cells>
+__global__ void __launch_bounds__(256) lr_encode_kernel(LrArgs p, double *__restrict__ partial, LrGrid g,
+                                                        Cells... cells) {
+  constexpr bool kCells = sizeof...(Cells) != 0;
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
   const int col = lane & 15;
@@ -132,17 +162,37 @@ __global__ void __launch_bounds__(256) lr_encode_kernel(LrArgs p, double *__rest
     sdb[t] = (raw && p.sd) ? p.sd[srcb[t]] : 1.0;
   }
 
-  const int64_t gw = (int64_t)blockIdx.x * kWaves + wave;
-  const int64_t nw = (int64_t)gridDim.x * kWaves;
-  const int64_t steps = (p.N + 3) / 4;
+  int64_t gw = (int64_t)blockIdx.x * kWaves + wave;
+  int64_t nw = (int64_t)gridDim.x * kWaves;
+  int64_t steps = (p.N + 3) / 4;
+  // kCells: the records are the cell's slice [first, first + count) of the permutation
+  [[maybe_unused]] const int64_t *perm = nullptr;
+  [[maybe_unused]] int64_t count = 0;
+  if constexpr (kCells) {
+    const LrCells cl = (cells, ...);
+    const int64_t cell = cl.c0 + (int64_t)(blockIdx.x / (unsigned)cl.nbc);
+    const int64_t first = cl.cell_start[cell];
+    perm = cl.perm + first;
+    count = cl.cell_start[cell + 1] - first;
+    gw = (int64_t)(blockIdx.x % (unsigned)cl.nbc) * kWaves + wave;
+    nw = (int64_t)cl.nbc * kWaves;
+    steps = (count + 3) / 4;
+  }
   for (int64_t s = gw; s < steps; s += nw) {
-    const int64_t row = s * 4 + kk;
+    int64_t row = s * 4 + kk;
+    bool live;
+    if constexpr (kCells) {
+      live = row < count;
+      row = live ? perm[row] : 0;
+    } else {
+      live = row < p.N;
+    }
     double va[TA], vb[TB];
     double wi = 0.0, gi = 0.0;
     double ga[TA];
 #pragma unroll
     for (int t = 0; t < TA; t++) ga[t] = 0.0;
-    if (row < p.N) {
+    if (live) {
       if constexpr (kMulti) {
         wi = p.wb;
         const double *yr = p.Y + row * p.ldy;
@@ -207,30 +257,38 @@ __global__ void __launch_bounds__(256) lr_encode_kernel(LrArgs p, double *__rest
   }
 }
 
-template <int TA, int TB, bool kDiag = false, bool kMulti = false>
+// cells: the grouped kernels over n_blocks = cells of the window x record blocks per cell
+template <int TA, int TB, bool kDiag = false, bool kMulti = false, bool kCells = false>
 void launch_tiles(hipStream_t stream, const LrArgs &a, double *partial, int n_blocks, int ta0, int tb0, int nga,
-                  int ngb, int P) {
+                  int ngb, int P, const LrCells *cells = nullptr) {
   if (nga <= 0 || ngb <= 0) return;
   const LrGrid g{ta0, tb0, P};
-  hipLaunchKernelGGL((lr_encode_kernel<TA, TB, kDiag, kMulti>), dim3(n_blocks, nga, ngb), dim3(256), 0, stream, a, partial,
-                     g);
+  if constexpr (kCells)
+    hipLaunchKernelGGL((lr_encode_kernel<TA, TB, kDiag, kMulti, LrCells>), dim3(n_blocks, nga, ngb), dim3(256), 0,
+                       stream, a, partial, g, *cells);
+  else
+    hipLaunchKernelGGL((lr_encode_kernel<TA, TB, kDiag, kMulti>), dim3(n_blocks, nga, ngb), dim3(256), 0, stream, a,
+                       partial, g);
 }
 
 // run-time tile-block shape (tan x tbn tiles, each 1..3; 0 = nothing to launch) -> instantiation
-template <int TA, bool kMulti>
+template <int TA, bool kMulti, bool kCells>
 void launch_cols(hipStream_t stream, const LrArgs &a, double *partial, int n_blocks, int ta0, int tb0, int nga,
-                 int ngb, int P, int tbn) {
-  if (tbn == 1) launch_tiles<TA, 1, false, kMulti>(stream, a, partial, n_blocks, ta0, tb0, nga, ngb, P);
-  else if (tbn == 2) launch_tiles<TA, 2, false, kMulti>(stream, a, partial, n_blocks, ta0, tb0, nga, ngb, P);
-  else if (tbn == 3) launch_tiles<TA, 3, false, kMulti>(stream, a, partial, n_blocks, ta0, tb0, nga, ngb, P);
+                 int ngb, int P, int tbn, const LrCells *cells) {
+  if (tbn == 1)
+    launch_tiles<TA, 1, false, kMulti, kCells>(stream, a, partial, n_blocks, ta0, tb0, nga, ngb, P, cells);
+  else if (tbn == 2)
+    launch_tiles<TA, 2, false, kMulti, kCells>(stream, a, partial, n_blocks, ta0, tb0, nga, ngb, P, cells);
+  else if (tbn == 3)
+    launch_tiles<TA, 3, false, kMulti, kCells>(stream, a, partial, n_blocks, ta0, tb0, nga, ngb, P, cells);
 }
 
-template <bool kMulti>
+template <bool kMulti, bool kCells>
 void launch_rows(hipStream_t stream, const LrArgs &a, double *partial, int n_blocks, int ta0, int tb0, int nga,
-                 int ngb, int P, int tan, int tbn) {
-  if (tan == 1) launch_cols<1, kMulti>(stream, a, partial, n_blocks, ta0, tb0, nga, ngb, P, tbn);
-  else if (tan == 2) launch_cols<2, kMulti>(stream, a, partial, n_blocks, ta0, tb0, nga, ngb, P, tbn);
-  else if (tan == 3) launch_cols<3, kMulti>(stream, a, partial, n_blocks, ta0, tb0, nga, ngb, P, tbn);
+                 int ngb, int P, int tan, int tbn, const LrCells *cells) {
+  if (tan == 1) launch_cols<1, kMulti, kCells>(stream, a, partial, n_blocks, ta0, tb0, nga, ngb, P, tbn, cells);
+  else if (tan == 2) launch_cols<2, kMulti, kCells>(stream, a, partial, n_blocks, ta0, tb0, nga, ngb, P, tbn, cells);
+  else if (tan == 3) launch_cols<3, kMulti, kCells>(stream, a, partial, n_blocks, ta0, tb0, nga, ngb, P, tbn, cells);
 }
 
 // Padded output width: 48 while level 2 and the level-1 rows (one per label
@@ -260,30 +318,32 @@ int lr_padded(int D, int level1) {
 // 48 fb + 16 rb < 48 Y): always launched.
 // Every launched tile-block is the same instantiation over the same record
 // blocks as in the full plan, so what it writes is the same bits.
-template <bool kMulti>
-int launch(void *stream_, const LrArgs &a, double *partial, int n_blocks, int P, bool upper = false) {
+template <bool kMulti, bool kCells = false>
+int launch(void *stream_, const LrArgs &a, double *partial, int n_blocks, int P, bool upper = false,
+           const LrCells *cells = nullptr) {
   const int D = a.dx + a.aug;
   const int l1 = a.level1 ? a.T : 0;
   if (a.dx <= 0 || n_blocks <= 0 || a.T < 1 || a.T > 64 || P != lr_padded(D, l1)) return -2;
   if (kMulti ? (!a.Y || a.ldy < 0) : ((a.level1 || !a.w) && !a.y)) return -2;
+  if (kCells != (cells != nullptr)) return -2;
   hipStream_t stream = (hipStream_t)stream_;
   if (P == kD) {
-    launch_tiles<kTiles, kTiles, true, kMulti>(stream, a, partial, n_blocks, 0, 0, 1, 1, P);
+    launch_tiles<kTiles, kTiles, true, kMulti, kCells>(stream, a, partial, n_blocks, 0, 0, 1, 1, P, cells);
   } else {
     const int ntr = P / kTile, ntc = (D + kTile - 1) / kTile;
     const int fa = ntr / kTiles, ra = ntr % kTiles, fb = ntc / kTiles, rb = ntc % kTiles;
     if (!upper) {
-      launch_tiles<kTiles, kTiles, false, kMulti>(stream, a, partial, n_blocks, 0, 0, fa, fb, P);
+      launch_tiles<kTiles, kTiles, false, kMulti, kCells>(stream, a, partial, n_blocks, 0, 0, fa, fb, P, cells);
     } else {
       for (int Y = 0; Y < fa; Y++) {
         const int z0 = (l1 && kD * (Y + 1) > D) ? 0 : Y;  // a tile-block row with level-1 rows: whole
-        launch_tiles<kTiles, kTiles, false, kMulti>(stream, a, partial, n_blocks, Y * kTiles, z0 * kTiles, 1, fb - z0,
-                                                    P);
+        launch_tiles<kTiles, kTiles, false, kMulti, kCells>(stream, a, partial, n_blocks, Y * kTiles, z0 * kTiles, 1,
+                                                            fb - z0, P, cells);
       }
     }
-    launch_rows<kMulti>(stream, a, partial, n_blocks, 0, fb * kTiles, fa, 1, P, kTiles, rb);
-    launch_rows<kMulti>(stream, a, partial, n_blocks, fa * kTiles, 0, 1, fb, P, ra, kTiles);
-    launch_rows<kMulti>(stream, a, partial, n_blocks, fa * kTiles, fb * kTiles, 1, 1, P, ra, rb);
+    launch_rows<kMulti, kCells>(stream, a, partial, n_blocks, 0, fb * kTiles, fa, 1, P, kTiles, rb, cells);
+    launch_rows<kMulti, kCells>(stream, a, partial, n_blocks, fa * kTiles, 0, 1, fb, P, ra, kTiles, cells);
+    launch_rows<kMulti, kCells>(stream, a, partial, n_blocks, fa * kTiles, fb * kTiles, 1, 1, P, ra, rb, cells);
   }
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) {
@@ -378,6 +438,34 @@ extern "C" int dx_lr_encode_multi(void *stream, const double *X, int64_t ldx, in
   if (T < 1 || T > 64 || (N > 1 && ldy < T)) return -2;
   LrArgs a{X, ldx, N, dx, 1, mean, sd, nullptr, nullptr, 0.0, wb, 1, Y, ldy, T};
   return launch<true>(stream, a, partial, n_blocks, P, upper != 0);
+}
+
+// Grouped encoder (SQL WHERE / GROUP BY cohorts): the fused encoder per cell of
+// one DP's records, for the window [c0, c0 + cw) of its G cells.  perm [kept
+// rows] lists the rows that belong to a cell, grouped by cell with the record
+// order kept inside a cell, cell_start [G + 1] the cells' bounds in it (device
+// arrays; every perm entry in [0, N), cell_start non-decreasing from 0).  Every
+// cell gets nbc record blocks whatever its size (nbc comes from shapes the host
+// knows, so nothing is copied back): partial [cw][nbc][P][P], a block without
+// records writes zeros.  T = 1: labels y [N], the single-label kernels with the
+// level-2 weight wb; T >= 2: labels Y [N][T] with row stride ldy, the
+// multi-target kernels.  upper != 0: the packed layout's launch plan.  One cell
+// holding rows 0..N-1 in order with nbc record blocks is dx_lr_encode with
+// n_blocks = nbc, the same bits.
+extern "C" int dx_lr_encode_cells(void *stream, const double *X, int64_t ldx, int64_t N, int dx, const double *mean,
+                                  const double *sd, const double *y, const double *Y, int64_t ldy, int T, double wb,
+                                  const int64_t *perm, const int64_t *cell_start, int64_t c0, int64_t cw, int nbc,
+                                  double *partial, int P, int upper) {
+  if (!perm || !cell_start || c0 < 0 || cw < 1 || nbc < 1 || cw * nbc > 0x7fffffff) return -2;
+  const LrCells cl{perm, cell_start, c0, nbc};
+  const int n_blocks = (int)(cw * nbc);
+  if (T == 1) {
+    LrArgs a{X, ldx, N, dx, 1, mean, sd, nullptr, y, 0.0, wb, 1, nullptr, 0, 1};
+    return launch<false, true>(stream, a, partial, n_blocks, P, upper != 0, &cl);
+  }
+  if (T < 2 || T > 64 || (N > 1 && ldy < T)) return -2;
+  LrArgs a{X, ldx, N, dx, 1, mean, sd, nullptr, nullptr, 0.0, wb, 1, Y, ldy, T};
+  return launch<true, true>(stream, a, partial, n_blocks, P, upper != 0, &cl);
 }
 
 // Block partials -> the packed integer vector a DP encrypts, in one launch:

@@ -259,6 +259,101 @@ def encode_coefficients_int_many(Xs: list, ys: list, params: LogisticRegressionP
     return round_precision(lv, params.PrecisionApproxCoefficients)
 
 
+# ----------------------------------------------------------------------------- cohorts (SQL WHERE / GROUP BY)
+def cell_ids(K: torch.Tensor, plan) -> tuple:
+    """The cell of every record under a query's SQL plan, from the DP's key
+    table K [N, >= plan.width] int64 -> ([N] int64, G): the ``row_group`` rule
+    of the grouped moments in torch.  A record failing a Where term or with a
+    GroupBy value outside [0, V_i) gets G (dropped); otherwise the mixed-radix
+    number of its GroupBy values, first column most significant
+    (``all_possible_groups`` order); without GroupBy the one cell 0."""
+    keep = torch.ones(K.shape[0], dtype=torch.bool, device=K.device)
+    for col, val in plan.where:
+        keep &= K[:, col] == val
+    key = torch.zeros(K.shape[0], dtype=torch.int64, device=K.device)
+    G = 1
+    for col, card in plan.group_by:
+        v = K[:, col]
+        keep &= (v >= 0) & (v < card)
+        key = key * card + v
+        G *= card
+    return torch.where(keep, key, torch.full_like(key, G)), G
+
+
+def _cohort_terms(params, plan):
+    """(keys, filters) of the native grouped ops for a SQL plan, after the cohort rules."""
+    if params.K != 2 or not (params.Means and params.StandardDeviations):
+        raise ValueError("logistic regression over SQL cohorts needs K = 2 and global Means and StandardDeviations")
+    return [(c, 0, v) for c, v in plan.group_by], list(plan.where)
+
+
+def _key_table(K, n: int, plan, device) -> torch.Tensor:
+    if K is None:
+        raise ValueError("records without a key table for a query with SQL")
+    K = torch.as_tensor(K, device=device)
+    if K.dim() != 2 or K.dtype != torch.int64 or K.shape[0] != n:
+        raise ValueError(f"key table of shape {tuple(K.shape)} ({K.dtype}) for {n} records: [N, width] int64")
+    if K.shape[1] < plan.width:
+        raise ValueError(f"key table has {K.shape[1]} columns, the SQL query reads {plan.width}")
+    return K if K.shape[1] <= 1 or K.stride(1) == 1 else K.contiguous()
+
+
+def encode_coefficients_int_cells_many(Xs: list, ys: list, Ks: list, params: LogisticRegressionParameters, plan):
+    """``encode_coefficients_int`` per cell of the query's WHERE / GROUP BY, for
+    several DPs -> [n_dp, G, n_coeffs] int64 (G = the product of the GroupBy
+    cardinalities, 1 without GroupBy).  ``Ks[i]`` [N_i, width] int64 is DP i's
+    key table, row r the key columns of record r of (Xs[i], ys[i]); cell
+    membership is ``cell_ids``.  Standardisation is the query's global Means /
+    StandardDeviations, K = 2; an empty cell (and a DP without records) is all
+    zeros.  Records on a GPU: the grouped fp64-MFMA encoder
+    (``native.lr_encode_cells_many`` / ``..._packed_many``), one batch for the
+    DPs.  Host: ``cell_ids``, then ``approx_coefficients`` on each cell's
+    records -- the model the kernels are tested against."""
+    keys, filters = _cohort_terms(params, plan)
+    T = n_targets(params)
+    d = params.NbrFeatures
+    D = d + 1
+    n_out = n_coeffs(d, 2, params.Packing, params.NbrTargets)
+    G = 1
+    for _, v in plan.group_by:
+        G *= v
+    live = [i for i, X in enumerate(Xs) if X is not None and len(X) > 0]
+    dev = Xs[live[0]].device if live else torch.device("cpu")
+    out = torch.zeros((len(Xs), G, n_out), dtype=torch.int64, device=dev)
+    if not live:
+        return out
+    lX = [Xs[i].to(torch.float64) for i in live]
+    lX = [X if X.dim() != 2 or X.stride(1) == 1 else X.contiguous() for X in lX]
+    ly = [_label_matrix(torch.as_tensor(ys[i], device=dev), T) for i in live]
+    lK = [_key_table(Ks[i], lX[j].shape[0], plan, dev) for j, i in enumerate(live)]
+    if any(X.dim() != 2 or X.shape[1] != d for X in lX):
+        raise ValueError(f"records of another width than the query's {d} features")
+    if dev.type == "cuda":
+        if params.Packing == 1:
+            vals = nt.lr_encode_cells_packed_many(lX, ly, lK, params.Means, params.StandardDeviations, -1.0, keys,
+                                                  filters, params.PrecisionApproxCoefficients)
+        else:
+            tot = nt.lr_encode_cells_many(lX, ly, lK, params.Means, params.StandardDeviations, -1.0, keys, filters)
+            lv = torch.cat([tot[:, :, D:D + T, :D].reshape(len(lX), G, -1), tot[:, :, :D, :D].reshape(len(lX), G, -1)],
+                           2)
+            vals = round_precision(lv, params.PrecisionApproxCoefficients)
+        out[torch.as_tensor(live, device=dev)] = vals
+        return out
+    for X, y, K, i in zip(lX, ly, lK, live):
+        ids, _ = cell_ids(K, plan)
+        for c in ids.unique().tolist():
+            if c < G:
+                rows = (ids == c).nonzero().reshape(-1)
+                out[i, c] = encode_coefficients_int(X.index_select(0, rows), y.index_select(0, rows), params)
+    return out
+
+
+def encode_coefficients_int_cells(X: torch.Tensor, y: torch.Tensor, K: torch.Tensor,
+                                  params: LogisticRegressionParameters, plan) -> torch.Tensor:
+    """One DP's ``encode_coefficients_int_cells_many`` -> [G, n_coeffs] int64."""
+    return encode_coefficients_int_cells_many([X], [y], [K], params, plan)[0]
+
+
 def _label_matrix(y: torch.Tensor, T: int) -> torch.Tensor:
     """Labels as the fused encoder takes them: [N] for one target, [N, T] for several."""
     if T == 1:
@@ -480,24 +575,43 @@ def find_minimum_weights_with_encryption(encrypted: list, secret: int, initial_w
     return w, [a.tolist() for a in approx]
 
 
-def decode_logistic_regression_values(vals, params: LogisticRegressionParameters) -> list:
+def cohort_records(vals, params: LogisticRegressionParameters) -> int:
+    """Records behind the aggregate of one SQL cell: level 2's entry (0, 0) is
+    sum (-1) * 1 * 1 = -n, the first level-2 value in both layouts, so
+    n = round(-v / PrecisionApproxCoefficients)."""
+    if params.K < 2:
+        raise ValueError("K = 1 carries no record count")
+    v = float(vals[n_targets(params) * (params.NbrFeatures + 1)])
+    return int(round(-v / params.PrecisionApproxCoefficients))
+
+
+def decode_logistic_regression_values(vals, params: LogisticRegressionParameters, cohort: bool = False) -> list:
+    """The weights of the decrypted aggregate ``vals``.  ``cohort``: the
+    aggregate of one cell of a query with SQL: the descent runs with the
+    cell's own record count (``cohort_records``) in place of NbrRecords, and an
+    empty cell decodes to NaN weights, as the other operations answer for an
+    empty group."""
     with timers.timed("GradientDescent", sync=False):
         approx = [a / params.PrecisionApproxCoefficients
                   for a in unpack(vals, params.NbrFeatures, params.K, params.Packing, n_targets(params))]
         D = params.NbrFeatures + 1
         init = list(params.InitialWeights or [0.0] * D)
         T = n_targets(params)
+        n_rec = params.NbrRecords
+        if cohort:
+            n_rec = cohort_records(vals, params)
+            if n_rec == 0:
+                return [float("nan")] * (T * D)
         if T == 1:
-            return find_minimum_weights(approx, init, params.NbrRecords, params.Lambda, params.Step,
-                                        params.MaxIterations)
+            return find_minimum_weights(approx, init, n_rec, params.Lambda, params.Step, params.MaxIterations)
         # one descent per target against the shared level 2; the weights target-major in one flat list
         if len(init) not in (D, T * D):
             raise ValueError(f"{len(init)} initial weights for {T} targets of {D} weights")
         out = []
         for t in range(T):
             w0 = init if len(init) == D else init[t * D:(t + 1) * D]
-            out += list(find_minimum_weights([approx[0][t]] + approx[1:], w0, params.NbrRecords, params.Lambda,
-                                             params.Step, params.MaxIterations))
+            out += list(find_minimum_weights([approx[0][t]] + approx[1:], w0, n_rec, params.Lambda, params.Step,
+                                             params.MaxIterations))
         return out
 
 

@@ -108,6 +108,8 @@ _SIGS = {
     "dx_lr_reduce_pack": [_P, _P, _L, _I, _I, _L, ctypes.c_double, _P, _P],
     "dx_lr_encode_multi": [_P, _P, _L, _L, _I, _P, _P, _P, _L, _I, ctypes.c_double, _P, _I, _I, _I],
     "dx_lr_reduce_pack_multi": [_P, _P, _L, _I, _I, _I, _L, ctypes.c_double, _P, _P],
+    "dx_lr_encode_cells": [_P, _P, _L, _L, _I, _P, _P, _P, _P, _L, _I, ctypes.c_double, _P, _P, _L, _L, _I, _P, _I,
+                           _I],
     "dx_g1_mul_glv256": [_P, _P, _P, _P, _P, _L, _I, _I, _I],
     "dx_glv_split": [_I, _P, _P, _P, _L],
     "dx_gt_t2_compress": [_I, _P, _P, _P, _P, _L],
@@ -145,6 +147,7 @@ _SIGS = {
     "dx_iter_round": [_I, _P, _P, _L, _P, _L, _P, _L, _I, _L, _L, _L, _L, _L, _P, _P],
     "dx_group_moments": [_I, _P, _P, _L, _I, _P, _L, _I, _P, _L, _P, _I, _P, _I, _P, _I, _L, _L, _P],
     "dx_group_moments_max_cells": [],
+    "dx_group_cells": [_I, _P, _P, _L, _I, _L, _P, _I, _P, _I, _P],
     "dx_sha256_rows": [_I, _P, _P, _L, _L, _L, _L, _P],
     "dx_sha256_segments": [_I, _P, _P, _L, _L, _L, _P],
     "dx_g1_aff_to_uv": [_I, _P, _P, _L],
@@ -1176,6 +1179,41 @@ GROUP_MOMENTS_MAX_GROUPS = 1 << 24
 GROUP_MOMENTS_MAX_CELLS = 5888
 
 
+def _group_terms(what: str, K, n_rows: int, of: str, keys, filters, bins=None):
+    """The checked key and filter terms of a grouped op over the key matrix K
+    -> (keys, filters, columns of K, G): at most 4 ``(column, offset,
+    cardinality)`` and 8 ``(column, value)``, every column inside K, K int64
+    with unit column stride and ``n_rows`` rows (those of ``of``), G = the
+    product of the cardinalities at most 2^24."""
+    keys = [tuple(int(x) for x in k) for k in keys]
+    filters = [tuple(int(x) for x in f) for f in filters]
+    if len(keys) > GROUP_MOMENTS_MAX_KEYS or any(len(k) != 3 for k in keys):
+        raise ValueError(f"{what}: {len(keys)} key columns (at most {GROUP_MOMENTS_MAX_KEYS} triples)")
+    if len(filters) > GROUP_MOMENTS_MAX_FILTERS or any(len(f) != 2 for f in filters):
+        raise ValueError(f"{what}: {len(filters)} filter terms (at most {GROUP_MOMENTS_MAX_FILTERS} pairs)")
+    if bins is not None:
+        keys = keys + [tuple(int(x) for x in bins)]
+        if len(keys[-1]) != 3:
+            raise ValueError(f"{what}: bins is one (column, offset, cardinality)")
+    CK = 0
+    if K is not None:
+        assert K.dtype == torch.int64 and K.dim() == 2 and (K.shape[1] <= 1 or K.stride(1) == 1)
+        if K.shape[0] != n_rows:
+            raise ValueError(f"{what}: K has {K.shape[0]} rows, {of} has {n_rows}")
+        CK = K.shape[1]
+    G = 1
+    for col, _, card in keys:
+        if card < 1 or card > GROUP_MOMENTS_MAX_GROUPS:
+            raise ValueError(f"{what}: cardinality {card}")
+        G *= card
+    if G > GROUP_MOMENTS_MAX_GROUPS:
+        raise ValueError(f"{what}: {G} groups (at most {GROUP_MOMENTS_MAX_GROUPS})")
+    for col in [k[0] for k in keys] + [f[0] for f in filters]:
+        if not 0 <= col < CK:
+            raise ValueError(f"{what}: column {col} of a {CK}-column key matrix")
+    return keys, filters, CK, G
+
+
 def group_moments(Z: torch.Tensor, K: torch.Tensor | None, seg_rows, pairs, keys=(), filters=(),
                   bins=None) -> torch.Tensor:
     """K14d (csrc/kernels/dx_group_moments.hip): ``int_moments`` filtered and
@@ -1202,32 +1240,7 @@ def group_moments(Z: torch.Tensor, K: torch.Tensor | None, seg_rows, pairs, keys
     pr = np.asarray(pairs, dtype=np.int16).reshape(-1, 2)
     if C > INT_MOMENTS_MAX_COLS or pr.size == 0 or pr.min() < 0 or pr.max() > C:
         raise ValueError(f"group_moments: {C} columns, pairs out of range")
-    keys = [tuple(int(x) for x in k) for k in keys]
-    filters = [tuple(int(x) for x in f) for f in filters]
-    if len(keys) > GROUP_MOMENTS_MAX_KEYS or any(len(k) != 3 for k in keys):
-        raise ValueError(f"group_moments: {len(keys)} key columns (at most {GROUP_MOMENTS_MAX_KEYS} triples)")
-    if len(filters) > GROUP_MOMENTS_MAX_FILTERS or any(len(f) != 2 for f in filters):
-        raise ValueError(f"group_moments: {len(filters)} filter terms (at most {GROUP_MOMENTS_MAX_FILTERS} pairs)")
-    if bins is not None:
-        keys = keys + [tuple(int(x) for x in bins)]
-        if len(keys[-1]) != 3:
-            raise ValueError("group_moments: bins is one (column, offset, cardinality)")
-    CK = 0
-    if K is not None:
-        assert K.dtype == torch.int64 and K.dim() == 2 and (K.shape[1] <= 1 or K.stride(1) == 1)
-        if K.shape[0] != Z.shape[0]:
-            raise ValueError(f"group_moments: K has {K.shape[0]} rows, Z has {Z.shape[0]}")
-        CK = K.shape[1]
-    G = 1
-    for col, _, card in keys:
-        if card < 1 or card > GROUP_MOMENTS_MAX_GROUPS:
-            raise ValueError(f"group_moments: cardinality {card}")
-        G *= card
-    if G > GROUP_MOMENTS_MAX_GROUPS:
-        raise ValueError(f"group_moments: {G} groups (at most {GROUP_MOMENTS_MAX_GROUPS})")
-    for col in [k[0] for k in keys] + [f[0] for f in filters]:
-        if not 0 <= col < CK:
-            raise ValueError(f"group_moments: column {col} of a {CK}-column key matrix")
+    keys, filters, CK, G = _group_terms("group_moments", K, Z.shape[0], "Z", keys, filters, bins)
     counts = np.asarray(seg_rows, dtype=np.int64).reshape(-1)
     n_dp, P = len(counts), pr.shape[0]
     if counts.sum() != Z.shape[0] or (n_dp and counts.min() < 0):
@@ -1510,6 +1523,189 @@ def lr_encode_packed_many(Xs: list, ys: list, mean, sd, wa: float, wb: float, pr
     (target-major), then the one shared upper triangle."""
     partial, D = _lr_launch_many(Xs, ys, mean, sd, wa, wb, True)
     return lr_reduce_pack(partial, D, precision, floats, _lr_targets(ys))
+
+
+# Cap of the grouped encoder's partial slab [cells of a window, record blocks
+# per cell, P, P]: at P = 48 a block is 18 KB, so the 4096 cells of the largest
+# GROUP BY are processed in windows instead of one ~75 MB slab per record block.
+LR_CELLS_MAX_SLAB_BYTES = 64 << 20
+
+
+def _lr_cell_blocks(N: int, G: int) -> int:
+    """Record blocks every cell of a DP with N records and G cells gets: those of
+    the ungrouped encoder for an even share of the records.  From shapes the
+    host knows, never from a cell's size (a cell holding more strides longer);
+    one cell: ``_lr_blocks(N)``."""
+    return _lr_blocks(-(-int(N) // max(1, int(G))))
+
+
+def group_cells(K: torch.Tensor | None, n_rows: int, keys=(), filters=(), device=None) -> torch.Tensor:
+    """The cell of every row of the key matrix K [rows, CK] -> [rows] int64
+    (dx_group_cells, ``group_moments``' membership rule and argument checks):
+    the mixed-radix group index over ``keys``, or G (the number of groups) for a
+    row that a filter term or an out-of-range key digit drops.  K is read in
+    place through its row stride; None without keys and filters (one cell)."""
+    keys, filters, CK, G = _group_terms("group_cells", K, n_rows, "the records", keys, filters)
+    if K is None:
+        return torch.zeros(n_rows, dtype=torch.int64, device=device)
+    cell = torch.empty(n_rows, dtype=torch.int64, device=K.device)
+    if n_rows == 0:
+        return cell
+    kd = np.ascontiguousarray(np.asarray(keys, dtype=np.int64).reshape(-1))
+    fd = np.ascontiguousarray(np.asarray(filters, dtype=np.int64).reshape(-1))
+    g, s = _ctx(K)
+    rc = _raw_call("dx_group_cells", g, s, _ptr(K, strided=True), K.stride(0) if CK else 0, CK, n_rows,
+                   kd.ctypes.data_as(_P), len(keys), fd.ctypes.data_as(_P), len(filters), _ptr(cell))
+    if rc == -2:
+        raise ValueError("group_cells: the entry refused its arguments")
+    if rc != 0:
+        raise RuntimeError(f"native op dx_group_cells failed (rc={rc})")
+    return cell
+
+
+def lr_cell_plan(K: torch.Tensor | None, n_rows: int, keys=(), filters=(), device=None):
+    """The cell plan of one DP's records -> (perm, cell_start, G): the rows that
+    belong to a cell, grouped by cell with the record order kept inside a cell
+    (a stable sort of ``group_cells``; dropped rows sort behind the last cell),
+    and the cells' bounds in it, [G + 1].  Device ops only: nothing is copied
+    to the host."""
+    G = 1
+    for k in keys:
+        G *= int(k[2])
+    cell = group_cells(K, n_rows, keys, filters, device)
+    ids, perm = torch.sort(cell, stable=True)
+    cell_start = torch.searchsorted(ids, torch.arange(G + 1, dtype=torch.int64, device=cell.device))
+    return perm, cell_start, G
+
+
+def _lr_cells_run(Xs: list, ys: list, Ks: list, mean, sd, wb: float, keys, filters, upper: bool, packed: bool,
+                  max_slab_bytes, finish, out: torch.Tensor):
+    """The grouped encoder DP by DP and window by window: ``finish(slab, dst)``
+    reduces the window's [cw, nbc, P, P] slab into ``dst = out[dp, c0:c0 + cw]``
+    (``packed``: with the packed reducer, which reads nothing the upper plan skips)."""
+    X0 = Xs[0]
+    dev = X0.device
+    dx = X0.shape[1]
+    if dx < 1:
+        raise ValueError("lr_encode needs at least one feature")
+    D = dx + 1
+    T = _lr_targets(ys)
+    P = _lr_padded(D + T)
+    if len(Ks) != len(Xs) or len(ys) != len(Xs):
+        raise ValueError("lr_encode_cells: one label tensor and one key matrix (or None) per DP")
+    mean = torch.as_tensor(mean, dtype=torch.float64).to(dev).contiguous()
+    sd = torch.as_tensor(sd, dtype=torch.float64).to(dev).contiguous()
+    assert mean.numel() == dx and sd.numel() == dx
+    _, s = _ctx(X0)
+    # what the reducers read and a launch plan leaves unwritten must be zero (see _lr_launch_many);
+    # every record block of every cell of a window is written, with zeros where it has no record
+    full = (upper and packed) or P == 48 or ((D + 15) // 16 == P // 16 and not upper)
+    for i, (X, y, K) in enumerate(zip(Xs, ys, Ks)):
+        assert X.is_cuda and X.dtype == torch.float64 and X.dim() == 2 and X.stride(1) == 1 and X.shape[1] == dx
+        N = X.shape[0]
+        if K is not None and K.device != dev:
+            raise ValueError(f"native op mixes devices {dev} and {K.device}")
+        perm, cell_start, G = lr_cell_plan(K, N, keys, filters, dev)
+        if G != out.shape[1]:
+            raise ValueError(f"lr_encode_cells: {G} cells for an output of {out.shape[1]}")
+        if N == 0:
+            out[i].zero_()
+            continue
+        y = y.to(device=dev, dtype=torch.float64)
+        if T == 1:
+            y = y.reshape(-1).contiguous()
+            assert y.numel() == N
+            yp, Yp, ldy = _ptr(y), None, 0
+        else:
+            if y.stride(1) != 1 or (N > 1 and y.stride(0) < T):
+                y = y.contiguous()
+            assert y.shape == (N, T)
+            yp, Yp, ldy = None, ctypes.c_void_p(y.data_ptr()), (y.stride(0) if N > 1 else T)
+        nbc = _lr_cell_blocks(N, G)
+        cw = int(max(1, min(G, int(max_slab_bytes) // (nbc * P * P * 8))))
+        slab = (torch.empty if full else torch.zeros)((cw, nbc, P, P), dtype=torch.float64, device=dev)
+        for c0 in range(0, G, cw):
+            w = min(cw, G - c0)
+            rc = _raw_call("dx_lr_encode_cells", s, ctypes.c_void_p(X.data_ptr()), X.stride(0), N, dx, _ptr(mean),
+                           _ptr(sd), yp, Yp, ldy, T, float(wb), _ptr(perm), _ptr(cell_start), c0, w, nbc,
+                           _ptr(slab), P, 1 if upper else 0)
+            if rc != 0:
+                raise RuntimeError(f"dx_lr_encode_cells failed rc={rc}")
+            finish(slab[:w], out[i, c0:c0 + w])
+
+
+def lr_encode_cells_many(Xs: list, ys: list, Ks: list, mean, sd, wb: float, keys=(), filters=(), *,
+                         upper: bool = False, max_slab_bytes: int = LR_CELLS_MAX_SLAB_BYTES) -> torch.Tensor:
+    """``lr_encode_many`` per cell of a WHERE / GROUP BY over the DPs' records
+    (dx_lr_encode_cells, the fused fp64-MFMA encoder with the rows read through
+    a cell plan) -> [n, G, P, P] totals: for cell c of DP i level 2 (weight
+    ``wb``) in [:D, :D] and level 1 in rows D..D+T-1, summed over the records of
+    the cell; an empty cell is zeros.  ``Ks[i]`` [N_i, CK] int64 holds the key
+    and filter columns of DP i's records row for row (read in place through its
+    row stride; None without keys and filters); ``keys`` / ``filters`` and their
+    limits are ``group_moments``'.  Per DP the cells are encoded in windows whose
+    partial slab stays within ``max_slab_bytes``; every window is finished by
+    dx_lr_reduce with the cells as items, so a cell is the same bits whatever
+    the windows and whichever DPs share the batch.  ``upper``: the packed
+    layout's launch plan (what it skips is left zero or unwritten).  One cell
+    and no filter: ``lr_encode_many``'s bits."""
+    n = len(Xs)
+    G = 1
+    for k in keys:
+        G *= int(k[2])
+    D = Xs[0].shape[1] + 1
+    P = _lr_padded(D + _lr_targets(ys))
+    out = torch.empty((n, G, P, P), dtype=torch.float64, device=Xs[0].device)
+
+    def finish(slab, dst):
+        w, nb = slab.shape[0], slab.shape[1]
+        _, s = _ctx(slab)
+        rc = _raw_call("dx_lr_reduce", s, _ptr(slab), nb, P * P, w, _ptr(dst))
+        if rc != 0:
+            raise RuntimeError(f"dx_lr_reduce failed rc={rc}")
+
+    _lr_cells_run(Xs, ys, Ks, mean, sd, wb, keys, filters, upper, False, max_slab_bytes, finish, out)
+    return out
+
+
+def lr_encode_cells_packed_many(Xs: list, ys: list, Ks: list, mean, sd, wb: float, keys=(), filters=(),
+                                precision: float = 1.0, *, floats: bool = False,
+                                max_slab_bytes: int = LR_CELLS_MAX_SLAB_BYTES):
+    """``lr_encode_packed_many`` per cell: the distinct-coefficient integer
+    vectors -> int64 [n, G, T*D + D(D+1)/2] (``floats``: and the unrounded fp64
+    values), the encoder's upper launch plan per window and ONE reduce + pack +
+    round launch (dx_lr_reduce_pack) per window with the cells as items.  Entry
+    (i, j), i <= j, of a cell is the same bits as ``lr_encode_cells_many``'s."""
+    n = len(Xs)
+    G = 1
+    for k in keys:
+        G *= int(k[2])
+    D = Xs[0].shape[1] + 1
+    T = _lr_targets(ys)
+    dev = Xs[0].device
+    out = torch.empty((n, G, lr_packed_len(D, T)), dtype=torch.int64, device=dev)
+    fout = torch.empty((n, G, lr_packed_len(D, T)), dtype=torch.float64, device=dev) if floats else None
+    P = _lr_padded(D + T)
+
+    def finish(slab, dst):
+        w, nb = slab.shape[0], slab.shape[1]
+        fdst = None
+        if floats:  # the float twin of the window's slice of out
+            off = (dst.data_ptr() - out.data_ptr()) // 8
+            fdst = fout.view(-1)[off: off + dst.numel()]
+        _, s = _ctx(slab)
+        name = "dx_lr_reduce_pack" if T == 1 else "dx_lr_reduce_pack_multi"
+        args = (s, _ptr(slab), nb, P, D) + ((T,) if T > 1 else ()) + (w, float(precision), _ptr(dst), _ptr(fdst))
+        rc = _raw_call(name, *args)
+        if rc != 0:
+            raise RuntimeError(f"dx_lr_reduce_pack failed rc={rc}")
+
+    _lr_cells_run(Xs, ys, Ks, mean, sd, wb, keys, filters, True, True, max_slab_bytes, finish, out)
+    if floats and any(X.shape[0] == 0 for X in Xs):
+        for i, X in enumerate(Xs):
+            if X.shape[0] == 0:
+                fout[i].zero_()
+    return (out, fout) if floats else out
 
 
 # ----------------------------------------------------------------------------- range proofs (K15/K16)

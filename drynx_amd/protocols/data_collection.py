@@ -210,20 +210,56 @@ def dp_encode_batch(ctx, sq, dps: list) -> dict:
     return _encode_batch_tail(ctx, sq, dps, vals, groups, pk)
 
 
+def generate_lr_keys(sq, dp_id: str, plan, n_rows: int) -> torch.Tensor:
+    """[n_rows, plan.width] int64 key table (host) a DP generates beside its
+    logistic-regression records for a query with SQL, from a generator of its
+    own seeded from the survey id + "/sql" (the records' draws are untouched),
+    column by column: a ``GroupBy[i]`` column is uniform in [0, V_i), every
+    other one uniform in [0, 3], as ``generate_sql_table`` fills its extra columns."""
+    gen = torch.Generator().manual_seed(_seed(sq.SurveyID + "/sql", dp_id))
+    cards = dict(plan.group_by)
+    cols = [torch.randint(0, cards.get(c, 4), (n_rows,), generator=gen, dtype=torch.int64) for c in range(plan.width)]
+    return torch.stack(cols, dim=1)
+
+
 def _lr_values(ctx, sq, dps: list, device) -> torch.Tensor:
     """[n_dp, n_out] int64 coefficient vectors of every DP's logistic-regression
-    data (the fused fp64-MFMA encoder per DP, no host round trip in between)."""
-    from ..models.logistic_regression import encode_coefficients_int, encode_coefficients_int_many, n_coeffs
+    data (the fused fp64-MFMA encoder per DP, no host round trip in between).
+    A query with SQL: [n_dp, ng, n_out], one vector per cell of its WHERE /
+    GROUP BY (the grouped encoder); ``ctx.dp_data[dp.id]`` is then (X, y, K)
+    with the key table K [N, >= plan.width] int64."""
+    from ..models.logistic_regression import (encode_coefficients_int, encode_coefficients_int_cells_many,
+                                              encode_coefficients_int_many, n_coeffs)
 
     op = sq.Query.Operation
     params = op.LRParameters
+    plan = sql_plan(sq.Query)  # None: a query without SQL
     data = []
     for dp in dps:
+        K = None
         if ctx.dp_data and dp.id in ctx.dp_data:
-            X, y = ctx.dp_data[dp.id]
+            rec = ctx.dp_data[dp.id]
+            if plan is not None and len(rec) < 3:
+                raise ValueError(f"DP {dp.id} has records without a key table, the SQL query reads "
+                                 f"{plan.width} key columns")
+            X, y = rec[0], rec[1]
+            if plan is not None:
+                K = torch.as_tensor(rec[2])
+                if K.dim() != 2 or K.shape[1] < plan.width:
+                    raise ValueError(f"DP {dp.id} has a key table of shape {tuple(K.shape)}, the SQL query reads "
+                                     f"{plan.width} key columns")
         else:
             X, y = generate_lr_data(params, device, torch.Generator().manual_seed(_seed(sq.SurveyID, dp.id)))
-        data.append((X, y))
+            if plan is not None:
+                K = generate_lr_keys(sq, dp.id, plan, X.shape[0])
+        data.append((X, y, K))
+    if plan is not None:
+        def t(v, dtype=None):
+            return None if v is None else torch.as_tensor(v, device=device, dtype=dtype)
+
+        return encode_coefficients_int_cells_many([t(X) for X, _, _ in data], [t(y) for _, y, _ in data],
+                                                  [t(K, torch.int64) for _, _, K in data], params, plan).to(device)
+    data = [(X, y) for X, y, _ in data]
     if device.type == "cuda":
         # every DP of the rank through the fused encoder at once: one reduction and
         # one rounding pass instead of ~20 launches per DP on the critical path

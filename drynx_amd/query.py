@@ -176,7 +176,13 @@ class QuerySQL:
       to the group of its values in those columns, in ``all_possible_groups``
       order, and a record with a value outside [0, V_i) is dropped;
     * ``Where`` without ``GroupBy``: the filtered answer is replicated over the
-      groups of ``GroupByValues`` as an unfiltered one is.
+      groups of ``GroupByValues`` as an unfiltered one is;
+    * ``logistic regression``: one model per cell (cohort).  The columns are
+      those of a DP's key table K [N, width] int64, row i the keys of record i
+      of its float features; ``Select`` must stay empty; LRParameters has K = 2
+      (level 2's first entry carries the cell's record count, with which the
+      querier descends) and global Means and StandardDeviations; an empty cell
+      decodes to NaN weights.
 
     All empty = the query without SQL, in every respect."""
     Select: list = field(default_factory=list)
@@ -210,8 +216,9 @@ def sql_column(name) -> int:
 @dataclass
 class SQLPlan:
     """A checked QuerySQL in column indices: ``select`` (the operation's input
-    columns), ``where`` [(column, value)], ``group_by`` [(column, cardinality)]
-    and the table ``width`` (1 + the largest referenced column)."""
+    columns; none for a logistic regression), ``where`` [(column, value)],
+    ``group_by`` [(column, cardinality)] and the table ``width`` (1 + the
+    largest referenced column)."""
     select: list
     where: list
     group_by: list
@@ -227,9 +234,16 @@ def sql_plan(q: "Query") -> Optional[SQLPlan]:
     n_in = max(1, q.Operation.NbrInput)
     if sql.Predicate:
         raise ValueError("SQL predicate set: only the conjunction of Where equalities is defined")
-    select = [sql_column(n) for n in sql.Select] if sql.Select else list(range(n_in))
-    if len(select) != n_in:
-        raise ValueError(f"SQL select lists {len(select)} columns, the operation reads {n_in}")
+    if q.Operation.NameOp == "logistic regression":
+        # the columns are those of a DP's key table, beside its float features
+        if sql.Select:
+            raise ValueError("SQL select with logistic regression: the features are the DP's float matrix, "
+                             "not table columns")
+        select = []
+    else:
+        select = [sql_column(n) for n in sql.Select] if sql.Select else list(range(n_in))
+        if len(select) != n_in:
+            raise ValueError(f"SQL select lists {len(select)} columns, the operation reads {n_in}")
     if len(sql.Where) > SQL_MAX_WHERE:
         raise ValueError(f"SQL where has more than {SQL_MAX_WHERE} terms")
     where = []
@@ -566,7 +580,18 @@ def _check_sql(sq: SurveyQuery) -> list:
     if name in ("bool_AND", "bool_OR"):
         msg.append(f"SQL with {name}: a DP's bit is its first record, not a statistic of its records")
     elif name == "logistic regression":
-        msg.append("SQL with logistic regression: its records are float features, not table columns")
+        lrp = q.Operation.LRParameters
+        if lrp is None:
+            msg.append("SQL with logistic regression: no LRParameters")
+            return msg
+        if lrp.K == 1:
+            msg.append("SQL with logistic regression: K = 1 carries no record count, an empty cell cannot be told "
+                       "from a real one")
+        elif lrp.K != 2:
+            msg.append(f"SQL with logistic regression: K = {lrp.K} has no fused encoder (K = 2 only)")
+        if not (lrp.Means and lrp.StandardDeviations):
+            msg.append("SQL with logistic regression: Means and StandardDeviations must be set (the "
+                       "standardisation is global; one per cell is not defined)")
     elif name not in SQL_OPERATIONS:
         msg.append(f"SQL with the operation {name}")
     if sq.IterBase:

@@ -86,7 +86,7 @@ class DrynxClient:
             with timers.timed("Decode"):
                 for g, cv in enumerate(partial.groups()):
                     groups.append(keys[g] if keys is not None else str(g))
-                    values.append(self.decode(cv.to(self.device), op))
+                    values.append(self.decode(cv.to(self.device), op, cohort=bool(sq.Query.SQL)))
             return groups, values
 
         # decoding overlaps the VNs' proof verification (own thread + stream)
@@ -94,14 +94,16 @@ class DrynxClient:
         groups, values = res.client_out
         return groups, values, res
 
-    def decode(self, cv: eg.CipherVector, op: Operation):
+    def decode(self, cv: eg.CipherVector, op: Operation, cohort: bool = False):
+        """``cohort``: the aggregate of one cell of a query with SQL (a logistic
+        regression then descends with the cell's own record count)."""
         if op.NameOp == "logistic regression":
             with timers.timed("Decryption"):
                 vals = [int(v) for v in eg.decrypt_auto(self.keypair.secret, cv, self.decrypt_bound).cpu().tolist()]
             self.last_plaintexts.append(vals)
             from ..models.logistic_regression import decode_logistic_regression_values
 
-            return decode_logistic_regression_values(vals, op.LRParameters)
+            return decode_logistic_regression_values(vals, op.LRParameters, cohort)
         return enc.decode(cv, self.keypair.secret, op, self.table)
 
     # ------------------------------------------------------------------ iterative min / max
