@@ -32,27 +32,24 @@
 // over the [blocks,P,P] slab, batched over the DPs of a rank) finishes
 // deterministically.
 //
-// Distinct-coefficient layout (query extension Packing = 1): level 2 is
-// symmetric, so only (i, j), i <= j, is sent.  dx_lr_encode_upper launches the
-// same instantiations but not the tile-blocks strictly below the diagonal
-// (unless they hold row D), and dx_lr_reduce_pack does block sum, gather of
-// [level 1, upper triangle] and the rounding to int64 in one launch.
-//
-// Several label columns (query extension NbrTargets = T): level 2's weight
-// y - y (-1)^2 - 1 = -1 does not depend on the label, so T binary models over
-// the same records share it.  dx_lr_encode_multi (the kMulti instantiations)
-// accumulates level 1 of target t, g_t = 2 Y[i][t] - 1, in row D + t: in the
-// spare rows of the one 48-row tile-block while D + T <= 48, in further row
-// tiles beyond.  The single-label instantiations are untouched by it.
-//
-// Cohorts (a query with SQL WHERE / GROUP BY): every coefficient sum is taken
-// per cell of a DP's records.  dx_lr_encode_cells launches the same tile-block
-// plan with the grouped instantiations (a trailing LrCells argument): a block
-// reads its cell's rows through a row permutation grouped by cell (made from
-// dx_group_cells' ids by a stable sort), the cells of a window are one more
-// factor of the record-block grid dimension, and the partials [cells, record
-// blocks, P, P] are finished by dx_lr_reduce / dx_lr_reduce_pack with the
-// cells as items.  The ungrouped instantiations are untouched by it.
+// One encoder entry, dx_lr_encode, with three independent options; each only
+// selects other instantiations of the one kernel template or fewer launches of
+// the same ones, so a value is the same bits whichever way it is asked for:
+//   upper plan (Packing = 1): level 2 is symmetric, so only (i, j), i <= j, is
+//     sent.  The tile-blocks strictly below the diagonal are not launched
+//     (unless they hold a level-1 row), and dx_lr_reduce_pack does block sum,
+//     gather of [level 1, upper triangle] and the rounding to int64 in one launch.
+//   label columns (NbrTargets = T >= 2): level 2's weight y - y (-1)^2 - 1 = -1
+//     does not depend on the label, so T binary models over the same records
+//     share it.  The kMulti instantiations accumulate level 1 of target t,
+//     g_t = 2 Y[i][t] - 1, in row D + t: in the spare rows of the one 48-row
+//     tile-block while D + T <= 48, in further row tiles beyond.
+//   cells (SQL WHERE / GROUP BY): every coefficient sum is taken per cell of a
+//     DP's records.  The grouped instantiations (a trailing LrCells argument)
+//     read a cell's rows through a row permutation grouped by cell (made from
+//     dx_group_cells' ids by a stable sort); the cells of a window are one more
+//     factor of the record-block grid dimension, and the partials [cells,
+//     record blocks, P, P] are finished by the reducers with the cells as items.
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <cstdio>
@@ -84,6 +81,13 @@ struct LrArgs {
   int64_t ldy;
   int T;               // level-1 rows (1 for the single-label entry points)
 };
+
+// N rows and nothing else (no augmentation, standardisation, weights, labels, level 1): an entry sets what it has
+LrArgs lr_rows(const double *X, int64_t ldx, int64_t N, int dx) {
+  LrArgs a{};
+  a.X = X, a.ldx = ldx, a.N = N, a.dx = dx, a.T = 1;
+  return a;
+}
 
 // Where one launch's tile-blocks sit in the PxP output: block (x, y, z) covers
 // row tiles ta0 + TA * y .. and column tiles tb0 + TB * z .. of record block x.
@@ -358,7 +362,8 @@ int launch(void *stream_, const LrArgs &a, double *partial, int n_blocks, int P,
 // partial: [n_blocks][P][P], P = lr_padded(D, 0).
 extern "C" int dx_lr_moments(void *stream, const double *X, const double *w, int64_t N, int D, double *partial,
                              int n_blocks, int P) {
-  LrArgs a{X, D, N, D, 0, nullptr, nullptr, w, nullptr, 0.0, 0.0, 0, nullptr, 0, 1};
+  LrArgs a = lr_rows(X, D, N, D);
+  a.w = w;
   return launch<false>(stream, a, partial, n_blocks, P);
 }
 
@@ -405,67 +410,46 @@ extern "C" int dx_lr_reduce(void *stream, const double *partial, int64_t nb, int
   return 0;
 }
 
-// Fused DP encoder: standardise + augment + level-1 (row D) + level-2 ((wa*y + wb) weights).
-// partial: [n_blocks][P][P], P = lr_padded(dx + 1, 1); block columns past the
-// last live column tile (all padding) are not written.
-extern "C" int dx_lr_encode(void *stream, const double *X, int64_t ldx, int64_t N, int dx, const double *mean,
-                            const double *sd, const double *y, double wa, double wb, double *partial, int n_blocks,
-                            int P) {
-  LrArgs a{X, ldx, N, dx, 1, mean, sd, nullptr, y, wa, wb, 1, nullptr, 0, 1};
-  return launch<false>(stream, a, partial, n_blocks, P);
-}
-
-// The upper launch plan of dx_lr_encode (same arguments, same kernels): the
-// tile-blocks strictly below the diagonal that do not hold the level-1 row D
-// are not launched, so their part of the slab is NOT written.  For the packed
-// reducer below, which reads only (i, j), i <= j, and row D.
-extern "C" int dx_lr_encode_upper(void *stream, const double *X, int64_t ldx, int64_t N, int dx, const double *mean,
-                                  const double *sd, const double *y, double wa, double wb, double *partial,
-                                  int n_blocks, int P) {
-  LrArgs a{X, ldx, N, dx, 1, mean, sd, nullptr, y, wa, wb, 1, nullptr, 0, 1};
-  return launch<false>(stream, a, partial, n_blocks, P, true);
-}
-
-// Multi-target encoder: T label columns over the same records share ONE level
-// 2 (its weight y - y (-1)^2 - 1 = -1 does not depend on the label, so it is
-// the constant wb here), and level 1 of target t, sum_i (2 Y[i][t] - 1) xa_i,
-// rides in row D + t.  Y: [N][T] doubles with row stride ldy; partial:
-// [n_blocks][P][P], P = lr_padded(dx + 1, T); upper != 0: the packed layout's
-// launch plan.  T = 1..64.
-extern "C" int dx_lr_encode_multi(void *stream, const double *X, int64_t ldx, int64_t N, int dx, const double *mean,
-                                  const double *sd, const double *Y, int64_t ldy, int T, double wb, double *partial,
-                                  int n_blocks, int P, int upper) {
-  if (T < 1 || T > 64 || (N > 1 && ldy < T)) return -2;
-  LrArgs a{X, ldx, N, dx, 1, mean, sd, nullptr, nullptr, 0.0, wb, 1, Y, ldy, T};
-  return launch<true>(stream, a, partial, n_blocks, P, upper != 0);
-}
-
-// Grouped encoder (SQL WHERE / GROUP BY cohorts): the fused encoder per cell of
-// one DP's records, for the window [c0, c0 + cw) of its G cells.  perm [kept
-// rows] lists the rows that belong to a cell, grouped by cell with the record
-// order kept inside a cell, cell_start [G + 1] the cells' bounds in it (device
+// Fused DP encoder: standardise + augment + level 1 + level 2 over the raw
+// records X [N][dx].  partial: [n_blocks][P][P], P = lr_padded(dx + 1, T); block
+// columns past the last live column tile (all padding) are not written.
+// T = 1: Y is the contiguous [N] label vector (ldy is ignored), level 1 in row
+// D, level-2 weight wa*y + wb.  T = 2..64: Y is [N][T] doubles with row stride
+// ldy, level 1 of target t, sum_i (2 Y[i][t] - 1) xa_i, in row D + t, and ONE
+// level 2 with the constant weight wb (the kMulti kernels; wa must be 0).
+// upper != 0: the packed layout's launch plan: the tile-blocks strictly below
+// the diagonal that hold no level-1 row are not launched, so their part of the
+// slab is NOT written.  For dx_lr_reduce_pack, which never reads it.
+// perm == null: n_blocks record blocks over rows 0..N-1 (cell_start, c0, nbc
+// are ignored).  perm != null: the grouped kernels, the encoder per cell for
+// the window [c0, c0 + cw) of a DP's G cells (wa must be 0).  perm [kept rows]
+// lists the rows that belong to a cell, grouped by cell with the record order
+// kept inside a cell, cell_start [G + 1] the cells' bounds in it (device
 // arrays; every perm entry in [0, N), cell_start non-decreasing from 0).  Every
 // cell gets nbc record blocks whatever its size (nbc comes from shapes the host
-// knows, so nothing is copied back): partial [cw][nbc][P][P], a block without
-// records writes zeros.  T = 1: labels y [N], the single-label kernels with the
-// level-2 weight wb; T >= 2: labels Y [N][T] with row stride ldy, the
-// multi-target kernels.  upper != 0: the packed layout's launch plan.  One cell
-// holding rows 0..N-1 in order with nbc record blocks is dx_lr_encode with
+// knows, so nothing is copied back), and n_blocks is the whole grid, cw * nbc:
+// a multiple of nbc.  partial: [cw][nbc][P][P], a block without records writes
+// zeros.  One cell holding rows 0..N-1 in order is the ungrouped call with
 // n_blocks = nbc, the same bits.
-extern "C" int dx_lr_encode_cells(void *stream, const double *X, int64_t ldx, int64_t N, int dx, const double *mean,
-                                  const double *sd, const double *y, const double *Y, int64_t ldy, int T, double wb,
-                                  const int64_t *perm, const int64_t *cell_start, int64_t c0, int64_t cw, int nbc,
-                                  double *partial, int P, int upper) {
-  if (!perm || !cell_start || c0 < 0 || cw < 1 || nbc < 1 || cw * nbc > 0x7fffffff) return -2;
+extern "C" int dx_lr_encode(void *stream, const double *X, int64_t ldx, int64_t N, int dx, const double *mean,
+                            const double *sd, const double *Y, int64_t ldy, int T, double wa, double wb,
+                            double *partial, int64_t n_blocks, int P, int upper, const int64_t *perm,
+                            const int64_t *cell_start, int64_t c0, int nbc) {
+  const bool multi = T != 1, cells = perm != nullptr;
+  if (T < 1 || T > 64 || (multi && N > 1 && ldy < T) || ((multi || cells) && wa != 0.0)) return -2;
+  if (n_blocks > 0x7fffffff || (cells && (!cell_start || c0 < 0 || nbc < 1 || n_blocks < nbc || n_blocks % nbc)))
+    return -2;
+  LrArgs a = lr_rows(X, ldx, N, dx);
+  a.aug = 1, a.mean = mean, a.sd = sd, a.wa = wa, a.wb = wb, a.level1 = 1, a.T = T;
+  if (multi) a.Y = Y, a.ldy = ldy;
+  else a.y = Y;
   const LrCells cl{perm, cell_start, c0, nbc};
-  const int n_blocks = (int)(cw * nbc);
-  if (T == 1) {
-    LrArgs a{X, ldx, N, dx, 1, mean, sd, nullptr, y, 0.0, wb, 1, nullptr, 0, 1};
-    return launch<false, true>(stream, a, partial, n_blocks, P, upper != 0, &cl);
-  }
-  if (T < 2 || T > 64 || (N > 1 && ldy < T)) return -2;
-  LrArgs a{X, ldx, N, dx, 1, mean, sd, nullptr, nullptr, 0.0, wb, 1, Y, ldy, T};
-  return launch<true, true>(stream, a, partial, n_blocks, P, upper != 0, &cl);
+  const int nb = (int)n_blocks;
+  const bool up = upper != 0;
+  if (multi && cells) return launch<true, true>(stream, a, partial, nb, P, up, &cl);
+  if (multi) return launch<true>(stream, a, partial, nb, P, up);
+  if (cells) return launch<false, true>(stream, a, partial, nb, P, up, &cl);
+  return launch<false>(stream, a, partial, nb, P, up);
 }
 
 // Block partials -> the packed integer vector a DP encrypts, in one launch:
@@ -527,8 +511,8 @@ __global__ void __launch_bounds__(256) lr_reduce_pack_kernel(const double *__res
 
 // partial: [n_items][nb][P][P]; out: int64 [n_items][T*D + D(D+1)/2]; fout: the
 // unrounded packed values (same shape, fp64) or null.
-extern "C" int dx_lr_reduce_pack_multi(void *stream, const double *partial, int64_t nb, int P, int D, int T,
-                                       int64_t n_items, double precision, int64_t *out, double *fout) {
+extern "C" int dx_lr_reduce_pack(void *stream, const double *partial, int64_t nb, int P, int D, int T,
+                                 int64_t n_items, double precision, int64_t *out, double *fout) {
   // rows 0..D+T-1 must lie inside the slab
   if (D <= 0 || T < 1 || T > 64 || P < D + T || nb <= 0 || n_items <= 0) return -2;
   const int64_t n = n_items * ((int64_t)T * D + (int64_t)D * (D + 1) / 2);
@@ -540,12 +524,6 @@ extern "C" int dx_lr_reduce_pack_multi(void *stream, const double *partial, int6
     return -1;
   }
   return 0;
-}
-
-// One label column: [level 1 (row D), upper triangle], D + D(D+1)/2 values.
-extern "C" int dx_lr_reduce_pack(void *stream, const double *partial, int64_t nb, int P, int D, int64_t n_items,
-                                 double precision, int64_t *out, double *fout) {
-  return dx_lr_reduce_pack_multi(stream, partial, nb, P, D, 1, n_items, precision, out, fout);
 }
 
 // Querier gradient descent for k = 2 (FindMinimumWeights, reference

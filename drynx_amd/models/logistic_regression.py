@@ -233,6 +233,39 @@ def round_precision(v: torch.Tensor, precision: float) -> torch.Tensor:
     return (torch.sign(x) * torch.floor(torch.abs(x) + 0.5)).to(torch.int64)
 
 
+def _standardisation(params: LogisticRegressionParameters, X: torch.Tensor):
+    """(means, sds): the query's global ones, or without them the records' own."""
+    if params.Means and params.StandardDeviations:
+        return params.Means, params.StandardDeviations
+    return compute_means_sds(X)
+
+
+def _gpu_coefficients_int(Xs: list, ys: list, params: LogisticRegressionParameters, Ks=None, plan=None):
+    """``encode_coefficients_int`` of a batch of DPs on the fused fp64-MFMA
+    encoder (K <= 2) -> [n, n_coeffs] int64; with the DPs' key tables ``Ks`` and
+    a SQL ``plan``, per cell -> [n, G, n_coeffs].  Xs: float64 records on one
+    GPU with unit column stride, ys: ``_label_matrix``.  A single DP is a batch
+    of one: the batch reducers give a DP the same bits alone or batched.
+    Level-2 weight: ypart = y - y*(-1)^2 - 1 = 0*y - 1."""
+    T = n_targets(params)
+    D = Xs[0].shape[1] + 1
+    m, s = _standardisation(params, Xs[0])
+    precision = params.PrecisionApproxCoefficients
+    if plan is not None:
+        keys, filters = _cohort_terms(params, plan)
+    if params.Packing == 1:
+        # distinct layout: the upper launch plan, then one reduce + pack + round launch
+        packed = nt.lr_encode_packed_many(Xs, ys, m, s, 0.0, -1.0, precision) if plan is None else \
+            nt.lr_encode_cells_packed_many(Xs, ys, Ks, m, s, -1.0, keys, filters, precision)
+        return packed[..., :T * D] if params.K == 1 else packed
+    tot = nt.lr_encode_many(Xs, ys, m, s, 0.0, -1.0) if plan is None else \
+        nt.lr_encode_cells_many(Xs, ys, Ks, m, s, -1.0, keys, filters)
+    lv = tot[..., D:D + T, :D].flatten(-2)  # target-major level 1
+    if params.K == 2:
+        lv = torch.cat([lv, tot[..., :D, :D].flatten(-2)], -1)
+    return round_precision(lv, precision)
+
+
 def encode_coefficients_int_many(Xs: list, ys: list, params: LogisticRegressionParameters):
     """``encode_coefficients_int`` of several DPs' records as one fused batch
     (one encoder launch per DP, one reduction, one rounding pass: the same
@@ -243,20 +276,9 @@ def encode_coefficients_int_many(Xs: list, ys: list, params: LogisticRegressionP
     d = Xs[0].shape[1] if Xs[0] is not None and Xs[0].dim() == 2 else -1
     if d < 1 or any(X is None or not X.is_cuda or X.dim() != 2 or X.shape[1] != d or len(X) == 0 for X in Xs):
         return None
-    T = n_targets(params)
-    D = d + 1
-    ys = [_label_matrix(y, T) for y in ys]
-    if params.Packing == 1:
-        # distinct layout: the upper launch plan per DP, then one reduce + pack + round launch
-        packed = nt.lr_encode_packed_many([X.to(torch.float64) for X in Xs], ys, params.Means,
-                                          params.StandardDeviations, 0.0, -1.0, params.PrecisionApproxCoefficients)
-        return packed[:, :T * D] if params.K == 1 else packed
-    tot = nt.lr_encode_many([X.to(torch.float64).contiguous() for X in Xs], ys, params.Means,
-                            params.StandardDeviations, 0.0, -1.0)
-    lv = tot[:, D, :D] if T == 1 else tot[:, D:D + T, :D].reshape(len(Xs), -1)  # target-major level 1
-    if params.K == 2:
-        lv = torch.cat([lv, tot[:, :D, :D].reshape(len(Xs), -1)], 1)
-    return round_precision(lv, params.PrecisionApproxCoefficients)
+    ys = [_label_matrix(y, n_targets(params)) for y in ys]
+    Xs = [X.to(torch.float64) for X in Xs]
+    return _gpu_coefficients_int(Xs if params.Packing == 1 else [X.contiguous() for X in Xs], ys, params)
 
 
 # ----------------------------------------------------------------------------- cohorts (SQL WHERE / GROUP BY)
@@ -329,15 +351,7 @@ def encode_coefficients_int_cells_many(Xs: list, ys: list, Ks: list, params: Log
     if any(X.dim() != 2 or X.shape[1] != d for X in lX):
         raise ValueError(f"records of another width than the query's {d} features")
     if dev.type == "cuda":
-        if params.Packing == 1:
-            vals = nt.lr_encode_cells_packed_many(lX, ly, lK, params.Means, params.StandardDeviations, -1.0, keys,
-                                                  filters, params.PrecisionApproxCoefficients)
-        else:
-            tot = nt.lr_encode_cells_many(lX, ly, lK, params.Means, params.StandardDeviations, -1.0, keys, filters)
-            lv = torch.cat([tot[:, :, D:D + T, :D].reshape(len(lX), G, -1), tot[:, :, :D, :D].reshape(len(lX), G, -1)],
-                           2)
-            vals = round_precision(lv, params.PrecisionApproxCoefficients)
-        out[torch.as_tensor(live, device=dev)] = vals
+        out[torch.as_tensor(live, device=dev)] = _gpu_coefficients_int(lX, ly, params, lK, plan)
         return out
     for X, y, K, i in zip(lX, ly, lK, live):
         ids, _ = cell_ids(K, plan)
@@ -371,30 +385,9 @@ def encode_coefficients_int(X: torch.Tensor, y: torch.Tensor, params: LogisticRe
     y = _label_matrix(y, T)
     if params.Packing == 1:
         return _encode_coefficients_int_packed(X, y, params)
-    if X.is_cuda and T > 1:
-        m, s = (params.Means, params.StandardDeviations) if params.Means and params.StandardDeviations \
-            else compute_means_sds(X)
-        tot = nt.lr_encode_many([X.contiguous()], [y], m, s, 0.0, -1.0)[0]
-        D = X.shape[1] + 1
-        levels = [tot[D:D + T, :D].reshape(-1)] + ([tot[:D, :D].reshape(-1)] if params.K == 2 else [])
-        return torch.cat([round_precision(lv, params.PrecisionApproxCoefficients) for lv in levels])
     if X.is_cuda and params.K <= 2:
-        # one fused pass over the records: standardise + augment + level 1 + level 2 (dx_lr_encode)
-        if params.Means and params.StandardDeviations:
-            m = torch.as_tensor(params.Means, dtype=torch.float64)
-            s = torch.as_tensor(params.StandardDeviations, dtype=torch.float64)
-        else:
-            m, s = compute_means_sds(X)
-        # level-2 weight ypart = y - y*(-1)^2 - 1 = 0*y - 1
-        lvl1, lvl2 = nt.lr_encode(X.contiguous(), y, m, s, 0.0, -1.0)
-        levels = [lvl1] if params.K == 1 else [lvl1, lvl2.reshape(-1)]
-        return torch.cat([round_precision(lv, params.PrecisionApproxCoefficients) for lv in levels])
-    if params.Means and params.StandardDeviations:
-        Xs = standardise_with(X, params.Means, params.StandardDeviations)
-    else:
-        Xs = standardise(X)
-    Xa = augment(Xs)
-    levels = approx_coefficients(Xa, y, params.K)
+        return _gpu_coefficients_int([X.contiguous()], [y], params)[0]
+    levels = approx_coefficients(augment(standardise_with(X, *_standardisation(params, X))), y, params.K)
     return torch.cat([round_precision(lv, params.PrecisionApproxCoefficients) for lv in levels])
 
 
@@ -402,22 +395,12 @@ def _encode_coefficients_int_packed(X: torch.Tensor, y: torch.Tensor, params) ->
     """``encode_coefficients_int`` in the distinct layout (Packing = 1)."""
     if params.K > 2:
         raise ValueError("distinct packing is defined for K <= 2 only")
-    d = X.shape[1]
     if X.is_cuda:
-        if params.Means and params.StandardDeviations:
-            m, s = params.Means, params.StandardDeviations
-        else:
-            m, s = compute_means_sds(X)
-        packed = nt.lr_encode_packed_many([X], [y], m, s, 0.0, -1.0, params.PrecisionApproxCoefficients)[0]
-        return packed[:n_targets(params) * (d + 1)] if params.K == 1 else packed
+        return _gpu_coefficients_int([X], [y], params)[0]
     # host: the cartesian levels as for Packing = 0, then the upper triangle
-    if params.Means and params.StandardDeviations:
-        Xs = standardise_with(X, params.Means, params.StandardDeviations)
-    else:
-        Xs = standardise(X)
-    levels = approx_coefficients(augment(Xs), y, params.K)
+    levels = approx_coefficients(augment(standardise_with(X, *_standardisation(params, X))), y, params.K)
     cart = torch.cat([round_precision(lv, params.PrecisionApproxCoefficients) for lv in levels])
-    return pack(cart, d, params.K)
+    return pack(cart, X.shape[1], params.K)
 
 
 def encode_logistic_regression(X, y, params: LogisticRegressionParameters, pk: eg.PublicKeyTable,

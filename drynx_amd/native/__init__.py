@@ -15,6 +15,7 @@ Tensor conventions (all int32 tensors carrying raw u32 limbs, little endian):
 """
 from __future__ import annotations
 
+import collections
 import ctypes
 import os
 import threading
@@ -102,14 +103,10 @@ _SIGS = {
     "dx_random_scalars": [_I, _P, _P, ctypes.c_uint32, _P, _L],
     "dx_sha256_chunks": [_I, _P, _P, _L, _L, _P],
     "dx_hash_to_g1": [_I, _P, _P, _P, _L, _P, _L],
-    "dx_lr_encode": [_P, _P, _L, _L, _I, _P, _P, _P, ctypes.c_double, ctypes.c_double, _P, _I, _I],
+    "dx_lr_encode": [_P, _P, _L, _L, _I, _P, _P, _P, _L, _I, ctypes.c_double, ctypes.c_double, _P, _L, _I, _I, _P, _P,
+                     _L, _I],
     "dx_lr_reduce": [_P, _P, _L, _L, _L, _P],
-    "dx_lr_encode_upper": [_P, _P, _L, _L, _I, _P, _P, _P, ctypes.c_double, ctypes.c_double, _P, _I, _I],
-    "dx_lr_reduce_pack": [_P, _P, _L, _I, _I, _L, ctypes.c_double, _P, _P],
-    "dx_lr_encode_multi": [_P, _P, _L, _L, _I, _P, _P, _P, _L, _I, ctypes.c_double, _P, _I, _I, _I],
-    "dx_lr_reduce_pack_multi": [_P, _P, _L, _I, _I, _I, _L, ctypes.c_double, _P, _P],
-    "dx_lr_encode_cells": [_P, _P, _L, _L, _I, _P, _P, _P, _P, _L, _I, ctypes.c_double, _P, _P, _L, _L, _I, _P, _I,
-                           _I],
+    "dx_lr_reduce_pack": [_P, _P, _L, _I, _I, _I, _L, ctypes.c_double, _P, _P],
     "dx_g1_mul_glv256": [_P, _P, _P, _P, _P, _L, _I, _I, _I],
     "dx_glv_split": [_I, _P, _P, _P, _L],
     "dx_gt_t2_compress": [_I, _P, _P, _P, _P, _L],
@@ -1382,82 +1379,130 @@ def _lr_targets(ys: list) -> int:
     return ts.pop()
 
 
-def _lr_launch_many(Xs: list, ys: list, mean, sd, wa: float, wb: float, upper: bool):
-    """One encoder call per DP into one [n, nb, P, P] partial slab (nb = the
-    longest DP's record blocks) -> (slab, D).  ``upper``: the packed layout's
-    launch plan (dx_lr_encode_upper), which leaves the tile-blocks strictly
-    below the diagonal unwritten.  Labels [N] (or [N, 1]): the single-label
-    kernels, level 1 in row D.  Labels [N, T], T >= 2 (rows may be strided):
-    dx_lr_encode_multi, level 1 of target t in row D + t, level-2 weight the
-    constant ``wb`` (``wa`` must be 0: no label-dependent level-2 weight)."""
+# What every DP of an encoder batch shares: raw features dx, D = dx + 1, label
+# columns T, slab width P, the device mean / sd and the stream.
+_LrPrep = collections.namedtuple("_LrPrep", "dx D T P mean sd stream")
+
+
+def _lr_prepare(Xs: list, ys: list, mean, sd, wa: float) -> _LrPrep:
     X0 = Xs[0]
-    dev = X0.device
     dx = X0.shape[1]
     if dx < 1:
         raise ValueError("lr_encode needs at least one feature")
-    D = dx + 1
     T = _lr_targets(ys)
     if T < 1:
         raise ValueError("lr_encode needs at least one label column")
     if T > 1 and float(wa) != 0.0:
         raise ValueError("lr_encode: several label columns share one level 2, so its weight cannot depend on a label")
-    P = _lr_padded(D + T)
-    mean = torch.as_tensor(mean, dtype=torch.float64).to(dev).contiguous()
-    sd = torch.as_tensor(sd, dtype=torch.float64).to(dev).contiguous()
+    mean = torch.as_tensor(mean, dtype=torch.float64).to(X0.device).contiguous()
+    sd = torch.as_tensor(sd, dtype=torch.float64).to(X0.device).contiguous()
     assert mean.numel() == dx and sd.numel() == dx
+    return _LrPrep(dx, dx + 1, T, _lr_padded(dx + 1 + T), mean, sd, _ctx(X0)[1])
+
+
+def _lr_labels(p: _LrPrep, X: torch.Tensor, y: torch.Tensor):
+    """One DP's labels as the encoder reads them -> (the tensor to keep alive
+    until the launch, its pointer, ldy).  T = 1: [N] contiguous.  T > 1: [N, T]
+    with unit column stride and a row stride >= T (a column slice of a wider
+    matrix is read in place), copied otherwise."""
+    assert X.is_cuda and X.dtype == torch.float64 and X.dim() == 2 and X.stride(1) == 1 and X.shape[1] == p.dx
+    N = X.shape[0]
+    y = y.to(device=X.device, dtype=torch.float64)
+    if p.T == 1:
+        y = y.reshape(-1).contiguous()
+        assert y.numel() == N
+        return y, ctypes.c_void_p(y.data_ptr()), 0
+    if y.stride(1) != 1 or (N > 1 and y.stride(0) < p.T):
+        y = y.contiguous()
+    assert y.shape == (N, p.T)
+    return y, ctypes.c_void_p(y.data_ptr()), (y.stride(0) if N > 1 else p.T)
+
+
+def _lr_slab_uninit(D: int, T: int, upper: bool, packed: bool, all_blocks: bool) -> bool:
+    """Whether a partial slab may be ``torch.empty`` rather than ``torch.zeros``.
+
+    Invariant: a slab is left uninitialised only when every record block of
+    every item is written (``all_blocks``) AND every element the reader will
+    read is written; otherwise it is zero-filled, so that what is read but
+    unwritten adds nothing.  A shorter DP's trailing blocks in a batch slab
+    are never written; every record block of every cell of a window is, with
+    zeros where it has no record.  Written are the live tiles: all of [48, 48]
+    when P = 48, else row tiles 0..P/16-1 (rows 0..D+T-1: every row tile holds
+    a live row) by column tiles 0..ceil(D/16)-1, minus, in the upper plan, the
+    tile-blocks strictly below the diagonal of tile-block rows that hold no
+    row >= D.  The full reader (``lr_reduce``) reads all of [P, P], of which a
+    wide launch leaves the column tiles past D unwritten: with T label columns
+    P grows with D + T while the column tiles stay ceil(D/16), so it needs
+    P = 48, or the full plan while the two counts agree.  The packed reader
+    (``lr_reduce_pack``, ``packed``) reads only (i, j), i <= j < D, which lies
+    on or above the diagonal, and rows D..D+T-1 at columns < D, whose
+    tile-block rows the upper plan launches whole: all written under either
+    plan.  What the upper plan skips and the padding columns are never read
+    by it, so they may stay uninitialised.
+
+    Reached today: the batch driver with (upper, packed) = (False, False) and
+    (True, True), ``all_blocks`` = the DPs have the same number of record
+    blocks; the grouped driver with (False, False), (True, True) and
+    (True, False) -- the upper plan under the full reader -- always with
+    ``all_blocks``."""
+    if not all_blocks:
+        return False
+    P = _lr_padded(D + T)
+    return packed or P == 48 or (not upper and (D + 15) // 16 == P // 16)
+
+
+def _lr_launch(p: _LrPrep, X: torch.Tensor, labels, wa: float, wb: float, slab: torch.Tensor, n_blocks: int,
+               upper: bool, cells=None) -> None:
+    """THE native encoder call (dx_lr_encode) into the first ``n_blocks``
+    [P, P] blocks of a slab the caller owns: one DP's records X with
+    ``labels = _lr_labels(p, X, y)`` in ``n_blocks`` record blocks, or, with
+    ``cells = (perm, cell_start, c0, nbc)``, a window of ``n_blocks / nbc`` of
+    its cells from cell c0 on.  ``upper``: the packed layout's launch plan,
+    which leaves the tile-blocks strictly below the diagonal unwritten."""
+    assert slab.is_contiguous() and slab.dtype == torch.float64 and slab.numel() >= n_blocks * p.P * p.P
+    perm, cell_start, c0, nbc = cells if cells is not None else (None, None, 0, 0)
+    rc = _raw_call("dx_lr_encode", p.stream, ctypes.c_void_p(X.data_ptr()), X.stride(0), X.shape[0], p.dx,
+                   _ptr(p.mean), _ptr(p.sd), labels[1], labels[2], p.T, float(wa), float(wb), _ptr(slab), n_blocks,
+                   p.P, 1 if upper else 0, _ptr(perm), _ptr(cell_start), c0, nbc)
+    if rc != 0:
+        raise RuntimeError(f"dx_lr_encode failed rc={rc}")
+
+
+def _lr_launch_many(Xs: list, ys: list, mean, sd, wa: float, wb: float, upper: bool):
+    """One encoder call per DP into one [n, nb, P, P] partial slab (nb = the
+    longest DP's record blocks) -> (slab, D).  ``upper``: the packed layout's
+    launch plan, for the packed reducer.  Labels [N] (or [N, 1]): level 1 in
+    row D.  Labels [N, T], T >= 2 (rows may be strided): level 1 of target t in
+    row D + t, level-2 weight the constant ``wb`` (``wa`` must be 0: no
+    label-dependent level-2 weight)."""
+    p = _lr_prepare(Xs, ys, mean, sd, wa)
     nbs = [_lr_blocks(X.shape[0]) for X in Xs]
     nb = max(nbs)
-    # Invariant: the slab is torch.empty only when every record block of every
-    # DP is written AND every element the reducer will read is written;
-    # otherwise it is zero-filled, so that what is read but unwritten adds
-    # nothing.  A shorter DP's trailing blocks are never written.  Written are
-    # the live tiles: all of [48, 48] when P = 48, else row tiles 0..P/16-1
-    # (rows 0..D+T-1: every row tile holds a live row) by column tiles
-    # 0..ceil(D/16)-1, minus, in the upper plan, the tile-blocks strictly below
-    # the diagonal of tile-block rows that hold no row >= D.  The full reducer
-    # reads all of [P, P], of which a wide launch leaves the column tiles past
-    # D unwritten: with T label columns P grows with D + T while the column
-    # tiles stay ceil(D/16), so this holds only while the two counts agree.
-    # The packed reducer reads only (i, j), i <= j < D, which lies on or above
-    # the diagonal, and rows D..D+T-1 at columns < D, whose tile-block rows the
-    # upper plan launches whole: all written.  What that plan skips and the
-    # padding columns are never read, so they may stay uninitialised.
-    full = all(b == nb for b in nbs) and (upper or P == 48 or (D + 15) // 16 == P // 16)
-    alloc = torch.empty if full else torch.zeros
-    partial = alloc((len(Xs), nb, P, P), dtype=torch.float64, device=dev)
-    _, s = _ctx(X0)
-    keep = []
-    name = "dx_lr_encode_multi" if T > 1 else ("dx_lr_encode_upper" if upper else "dx_lr_encode")
+    alloc = torch.empty if _lr_slab_uninit(p.D, p.T, upper, upper, all(b == nb for b in nbs)) else torch.zeros
+    partial = alloc((len(Xs), nb, p.P, p.P), dtype=torch.float64, device=Xs[0].device)
     for i, (X, y) in enumerate(zip(Xs, ys)):
-        assert X.is_cuda and X.dtype == torch.float64 and X.dim() == 2 and X.stride(1) == 1 and X.shape[1] == dx
-        N = X.shape[0]
-        y = y.to(device=dev, dtype=torch.float64)
-        # rows may be strided (a column slice of a wider matrix): the kernel takes the row stride
-        if T == 1:
-            y = y.reshape(-1).contiguous()
-            assert y.numel() == N
-            rc = _raw_call(name, s, ctypes.c_void_p(X.data_ptr()), X.stride(0), N, dx, _ptr(mean), _ptr(sd),
-                           _ptr(y), float(wa), float(wb), _ptr(partial[i]), nbs[i], P)
-        else:
-            if y.stride(1) != 1 or (N > 1 and y.stride(0) < T):
-                y = y.contiguous()
-            assert y.shape == (N, T)
-            rc = _raw_call(name, s, ctypes.c_void_p(X.data_ptr()), X.stride(0), N, dx, _ptr(mean), _ptr(sd),
-                           ctypes.c_void_p(y.data_ptr()), y.stride(0) if N > 1 else T, T, float(wb), _ptr(partial[i]),
-                           nbs[i], P, 1 if upper else 0)
-        keep.append(y)
-        if rc != 0:
-            raise RuntimeError(f"{name} failed rc={rc}")
-    return partial, D
+        _lr_launch(p, X, _lr_labels(p, X, y), wa, wb, partial[i], nbs[i], upper)
+    return partial, p.D
 
 
-def lr_reduce(partial: torch.Tensor) -> torch.Tensor:
+def _lr_out(what: str, out, shape: tuple, dtype, device) -> torch.Tensor:
+    """A reducer's destination: a new tensor, or the caller's after its checks."""
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    if tuple(out.shape) != shape or out.dtype != dtype or out.device != device or not out.is_contiguous():
+        raise ValueError(f"{what}: out is {tuple(out.shape)} {out.dtype} on {out.device}"
+                         f"{'' if out.is_contiguous() else ', not contiguous'}, needed {shape} {dtype} on {device}")
+    return out
+
+
+def lr_reduce(partial: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
     """Block partials [n, nb, P, P] -> totals [n, P, P] (dx_lr_reduce: block b
-    into accumulator b % 4, combined as (s0 + s1) + (s2 + s3))."""
+    into accumulator b % 4, combined as (s0 + s1) + (s2 + s3)), written into
+    ``out`` (contiguous [n, P, P], e.g. a slice of a larger result) if given."""
     assert partial.is_cuda and partial.dtype == torch.float64 and partial.dim() == 4 and partial.is_contiguous()
     n, nb, P, P2 = partial.shape
     assert P == P2 and n >= 1 and nb >= 1
-    out = torch.empty((n, P, P), dtype=torch.float64, device=partial.device)
+    out = _lr_out("lr_reduce", out, (n, P, P), torch.float64, partial.device)
     _, s = _ctx(partial)
     rc = _raw_call("dx_lr_reduce", s, _ptr(partial), nb, P * P, n, _ptr(out))
     if rc != 0:
@@ -1484,14 +1529,17 @@ def lr_packed_len(D: int, T: int = 1) -> int:
     return T * D + D * (D + 1) // 2
 
 
-def lr_reduce_pack(partial: torch.Tensor, D: int, precision: float, floats: bool = False, T: int = 1):
+def lr_reduce_pack(partial: torch.Tensor, D: int, precision: float, floats: bool = False, T: int = 1,
+                   out: torch.Tensor | None = None, fout: torch.Tensor | None = None):
     """Block partials [n, nb, P, P] (or [nb, P, P]: one item) -> the packed
     int64 vectors [n, D + D(D+1)/2] in ONE launch (dx_lr_reduce_pack): level 1
     from row D, then level 2's upper triangle row-major, summed over the
     blocks in dx_lr_reduce's order, times ``precision``, rounded half away from
     zero.  Reads only (i, j), i <= j < D, and row D of each block.
     ``floats``: also return the unrounded packed fp64 values.  ``T`` label
-    columns: [n, T*D + D(D+1)/2], level 1 of target t from row D + t."""
+    columns: [n, T*D + D(D+1)/2], level 1 of target t from row D + t.
+    ``out`` / ``fout`` (the latter with ``floats``): contiguous destinations
+    of those shapes, e.g. slices of a larger result."""
     if partial.dim() == 3:
         partial = partial[None]
     assert partial.is_cuda and partial.dtype == torch.float64 and partial.dim() == 4 and partial.is_contiguous()
@@ -1499,15 +1547,13 @@ def lr_reduce_pack(partial: torch.Tensor, D: int, precision: float, floats: bool
     D, T = int(D), int(T)
     if not (P == P2 and 1 <= D and 1 <= T and D + T <= P and n >= 1 and nb >= 1):
         raise ValueError(f"lr_reduce_pack: slab {tuple(partial.shape)} does not hold rows 0..{D + T - 1}")
-    dev = partial.device
-    out = torch.empty((n, lr_packed_len(D, T)), dtype=torch.int64, device=dev)
-    fout = torch.empty((n, lr_packed_len(D, T)), dtype=torch.float64, device=dev) if floats else None
+    if fout is not None and not floats:
+        raise ValueError("lr_reduce_pack: fout without floats")
+    shape = (n, lr_packed_len(D, T))
+    out = _lr_out("lr_reduce_pack", out, shape, torch.int64, partial.device)
+    fout = _lr_out("lr_reduce_pack", fout, shape, torch.float64, partial.device) if floats else None
     _, s = _ctx(partial)
-    if T == 1:
-        rc = _raw_call("dx_lr_reduce_pack", s, _ptr(partial), nb, P, D, n, float(precision), _ptr(out), _ptr(fout))
-    else:
-        rc = _raw_call("dx_lr_reduce_pack_multi", s, _ptr(partial), nb, P, D, T, n, float(precision), _ptr(out),
-                       _ptr(fout))
+    rc = _raw_call("dx_lr_reduce_pack", s, _ptr(partial), nb, P, D, T, n, float(precision), _ptr(out), _ptr(fout))
     if rc != 0:
         raise RuntimeError(f"dx_lr_reduce_pack failed rc={rc}")
     return (out, fout) if floats else out
@@ -1539,18 +1585,14 @@ def _lr_cell_blocks(N: int, G: int) -> int:
     return _lr_blocks(-(-int(N) // max(1, int(G))))
 
 
-def group_cells(K: torch.Tensor | None, n_rows: int, keys=(), filters=(), device=None) -> torch.Tensor:
-    """The cell of every row of the key matrix K [rows, CK] -> [rows] int64
-    (dx_group_cells, ``group_moments``' membership rule and argument checks):
-    the mixed-radix group index over ``keys``, or G (the number of groups) for a
-    row that a filter term or an out-of-range key digit drops.  K is read in
-    place through its row stride; None without keys and filters (one cell)."""
+def _group_cells(K: torch.Tensor | None, n_rows: int, keys, filters, device):
+    """``group_cells`` -> (cells, G)."""
     keys, filters, CK, G = _group_terms("group_cells", K, n_rows, "the records", keys, filters)
     if K is None:
-        return torch.zeros(n_rows, dtype=torch.int64, device=device)
+        return torch.zeros(n_rows, dtype=torch.int64, device=device), G
     cell = torch.empty(n_rows, dtype=torch.int64, device=K.device)
     if n_rows == 0:
-        return cell
+        return cell, G
     kd = np.ascontiguousarray(np.asarray(keys, dtype=np.int64).reshape(-1))
     fd = np.ascontiguousarray(np.asarray(filters, dtype=np.int64).reshape(-1))
     g, s = _ctx(K)
@@ -1560,7 +1602,16 @@ def group_cells(K: torch.Tensor | None, n_rows: int, keys=(), filters=(), device
         raise ValueError("group_cells: the entry refused its arguments")
     if rc != 0:
         raise RuntimeError(f"native op dx_group_cells failed (rc={rc})")
-    return cell
+    return cell, G
+
+
+def group_cells(K: torch.Tensor | None, n_rows: int, keys=(), filters=(), device=None) -> torch.Tensor:
+    """The cell of every row of the key matrix K [rows, CK] -> [rows] int64
+    (dx_group_cells, ``group_moments``' membership rule and argument checks):
+    the mixed-radix group index over ``keys``, or G (the number of groups) for a
+    row that a filter term or an out-of-range key digit drops.  K is read in
+    place through its row stride; None without keys and filters (one cell)."""
+    return _group_cells(K, n_rows, keys, filters, device)[0]
 
 
 def lr_cell_plan(K: torch.Tensor | None, n_rows: int, keys=(), filters=(), device=None):
@@ -1569,76 +1620,63 @@ def lr_cell_plan(K: torch.Tensor | None, n_rows: int, keys=(), filters=(), devic
     (a stable sort of ``group_cells``; dropped rows sort behind the last cell),
     and the cells' bounds in it, [G + 1].  Device ops only: nothing is copied
     to the host."""
-    G = 1
-    for k in keys:
-        G *= int(k[2])
-    cell = group_cells(K, n_rows, keys, filters, device)
+    cell, G = _group_cells(K, n_rows, keys, filters, device)
     ids, perm = torch.sort(cell, stable=True)
     cell_start = torch.searchsorted(ids, torch.arange(G + 1, dtype=torch.int64, device=cell.device))
     return perm, cell_start, G
 
 
-def _lr_cells_run(Xs: list, ys: list, Ks: list, mean, sd, wb: float, keys, filters, upper: bool, packed: bool,
-                  max_slab_bytes, finish, out: torch.Tensor):
-    """The grouped encoder DP by DP and window by window: ``finish(slab, dst)``
-    reduces the window's [cw, nbc, P, P] slab into ``dst = out[dp, c0:c0 + cw]``
-    (``packed``: with the packed reducer, which reads nothing the upper plan skips)."""
-    X0 = Xs[0]
-    dev = X0.device
-    dx = X0.shape[1]
-    if dx < 1:
-        raise ValueError("lr_encode needs at least one feature")
-    D = dx + 1
-    T = _lr_targets(ys)
-    P = _lr_padded(D + T)
+def _lr_cells_run(Xs: list, ys: list, Ks: list, mean, sd, wb: float, keys, filters, upper: bool, max_slab_bytes,
+                  pack=None):
+    """The grouped encoder DP by DP and window by window -> (out, fout).  Every
+    window's [cw, nbc, P, P] slab is reduced straight into ``out[dp, c0:c0 +
+    cw]``: by ``lr_reduce`` into totals [n, G, P, P], or, with ``pack =
+    (precision, floats)``, by ``lr_reduce_pack`` into the packed int64 vectors
+    [n, G, T*D + D(D+1)/2] (and their unrounded values ``fout``).  A DP
+    without records is zeros."""
+    p = _lr_prepare(Xs, ys, mean, sd, 0.0)
     if len(Ks) != len(Xs) or len(ys) != len(Xs):
         raise ValueError("lr_encode_cells: one label tensor and one key matrix (or None) per DP")
-    mean = torch.as_tensor(mean, dtype=torch.float64).to(dev).contiguous()
-    sd = torch.as_tensor(sd, dtype=torch.float64).to(dev).contiguous()
-    assert mean.numel() == dx and sd.numel() == dx
-    _, s = _ctx(X0)
-    # what the reducers read and a launch plan leaves unwritten must be zero (see _lr_launch_many);
-    # every record block of every cell of a window is written, with zeros where it has no record
-    full = (upper and packed) or P == 48 or ((D + 15) // 16 == P // 16 and not upper)
+    dev = Xs[0].device
+    precision, floats = pack if pack is not None else (None, False)
+    alloc = torch.empty if _lr_slab_uninit(p.D, p.T, upper, pack is not None, True) else torch.zeros
+    out = fout = None
     for i, (X, y, K) in enumerate(zip(Xs, ys, Ks)):
-        assert X.is_cuda and X.dtype == torch.float64 and X.dim() == 2 and X.stride(1) == 1 and X.shape[1] == dx
+        labels = _lr_labels(p, X, y)
         N = X.shape[0]
         if K is not None and K.device != dev:
             raise ValueError(f"native op mixes devices {dev} and {K.device}")
         perm, cell_start, G = lr_cell_plan(K, N, keys, filters, dev)
-        if G != out.shape[1]:
-            raise ValueError(f"lr_encode_cells: {G} cells for an output of {out.shape[1]}")
+        if out is None:  # G is the first plan's: the keys' cardinalities, the same for every DP
+            if pack is None:
+                out = torch.empty((len(Xs), G, p.P, p.P), dtype=torch.float64, device=dev)
+            else:
+                out = torch.empty((len(Xs), G, lr_packed_len(p.D, p.T)), dtype=torch.int64, device=dev)
+                fout = torch.empty(out.shape, dtype=torch.float64, device=dev) if floats else None
         if N == 0:
             out[i].zero_()
+            if fout is not None:
+                fout[i].zero_()
             continue
-        y = y.to(device=dev, dtype=torch.float64)
-        if T == 1:
-            y = y.reshape(-1).contiguous()
-            assert y.numel() == N
-            yp, Yp, ldy = _ptr(y), None, 0
-        else:
-            if y.stride(1) != 1 or (N > 1 and y.stride(0) < T):
-                y = y.contiguous()
-            assert y.shape == (N, T)
-            yp, Yp, ldy = None, ctypes.c_void_p(y.data_ptr()), (y.stride(0) if N > 1 else T)
         nbc = _lr_cell_blocks(N, G)
-        cw = int(max(1, min(G, int(max_slab_bytes) // (nbc * P * P * 8))))
-        slab = (torch.empty if full else torch.zeros)((cw, nbc, P, P), dtype=torch.float64, device=dev)
+        cw = int(max(1, min(G, int(max_slab_bytes) // (nbc * p.P * p.P * 8))))
+        slab = alloc((cw, nbc, p.P, p.P), dtype=torch.float64, device=dev)
         for c0 in range(0, G, cw):
             w = min(cw, G - c0)
-            rc = _raw_call("dx_lr_encode_cells", s, ctypes.c_void_p(X.data_ptr()), X.stride(0), N, dx, _ptr(mean),
-                           _ptr(sd), yp, Yp, ldy, T, float(wb), _ptr(perm), _ptr(cell_start), c0, w, nbc,
-                           _ptr(slab), P, 1 if upper else 0)
-            if rc != 0:
-                raise RuntimeError(f"dx_lr_encode_cells failed rc={rc}")
-            finish(slab[:w], out[i, c0:c0 + w])
+            _lr_launch(p, X, labels, 0.0, wb, slab, w * nbc, upper, (perm, cell_start, c0, nbc))
+            if pack is None:
+                lr_reduce(slab[:w], out=out[i, c0:c0 + w])
+            else:
+                lr_reduce_pack(slab[:w], p.D, precision, floats, p.T, out=out[i, c0:c0 + w],
+                               fout=fout[i, c0:c0 + w] if floats else None)
+    return out, fout
 
 
 def lr_encode_cells_many(Xs: list, ys: list, Ks: list, mean, sd, wb: float, keys=(), filters=(), *,
                          upper: bool = False, max_slab_bytes: int = LR_CELLS_MAX_SLAB_BYTES) -> torch.Tensor:
     """``lr_encode_many`` per cell of a WHERE / GROUP BY over the DPs' records
-    (dx_lr_encode_cells, the fused fp64-MFMA encoder with the rows read through
-    a cell plan) -> [n, G, P, P] totals: for cell c of DP i level 2 (weight
+    (the fused fp64-MFMA encoder with the rows read through a cell plan) ->
+    [n, G, P, P] totals: for cell c of DP i level 2 (weight
     ``wb``) in [:D, :D] and level 1 in rows D..D+T-1, summed over the records of
     the cell; an empty cell is zeros.  ``Ks[i]`` [N_i, CK] int64 holds the key
     and filter columns of DP i's records row for row (read in place through its
@@ -1649,23 +1687,7 @@ def lr_encode_cells_many(Xs: list, ys: list, Ks: list, mean, sd, wb: float, keys
     the windows and whichever DPs share the batch.  ``upper``: the packed
     layout's launch plan (what it skips is left zero or unwritten).  One cell
     and no filter: ``lr_encode_many``'s bits."""
-    n = len(Xs)
-    G = 1
-    for k in keys:
-        G *= int(k[2])
-    D = Xs[0].shape[1] + 1
-    P = _lr_padded(D + _lr_targets(ys))
-    out = torch.empty((n, G, P, P), dtype=torch.float64, device=Xs[0].device)
-
-    def finish(slab, dst):
-        w, nb = slab.shape[0], slab.shape[1]
-        _, s = _ctx(slab)
-        rc = _raw_call("dx_lr_reduce", s, _ptr(slab), nb, P * P, w, _ptr(dst))
-        if rc != 0:
-            raise RuntimeError(f"dx_lr_reduce failed rc={rc}")
-
-    _lr_cells_run(Xs, ys, Ks, mean, sd, wb, keys, filters, upper, False, max_slab_bytes, finish, out)
-    return out
+    return _lr_cells_run(Xs, ys, Ks, mean, sd, wb, keys, filters, upper, max_slab_bytes)[0]
 
 
 def lr_encode_cells_packed_many(Xs: list, ys: list, Ks: list, mean, sd, wb: float, keys=(), filters=(),
@@ -1676,35 +1698,7 @@ def lr_encode_cells_packed_many(Xs: list, ys: list, Ks: list, mean, sd, wb: floa
     values), the encoder's upper launch plan per window and ONE reduce + pack +
     round launch (dx_lr_reduce_pack) per window with the cells as items.  Entry
     (i, j), i <= j, of a cell is the same bits as ``lr_encode_cells_many``'s."""
-    n = len(Xs)
-    G = 1
-    for k in keys:
-        G *= int(k[2])
-    D = Xs[0].shape[1] + 1
-    T = _lr_targets(ys)
-    dev = Xs[0].device
-    out = torch.empty((n, G, lr_packed_len(D, T)), dtype=torch.int64, device=dev)
-    fout = torch.empty((n, G, lr_packed_len(D, T)), dtype=torch.float64, device=dev) if floats else None
-    P = _lr_padded(D + T)
-
-    def finish(slab, dst):
-        w, nb = slab.shape[0], slab.shape[1]
-        fdst = None
-        if floats:  # the float twin of the window's slice of out
-            off = (dst.data_ptr() - out.data_ptr()) // 8
-            fdst = fout.view(-1)[off: off + dst.numel()]
-        _, s = _ctx(slab)
-        name = "dx_lr_reduce_pack" if T == 1 else "dx_lr_reduce_pack_multi"
-        args = (s, _ptr(slab), nb, P, D) + ((T,) if T > 1 else ()) + (w, float(precision), _ptr(dst), _ptr(fdst))
-        rc = _raw_call(name, *args)
-        if rc != 0:
-            raise RuntimeError(f"dx_lr_reduce_pack failed rc={rc}")
-
-    _lr_cells_run(Xs, ys, Ks, mean, sd, wb, keys, filters, True, True, max_slab_bytes, finish, out)
-    if floats and any(X.shape[0] == 0 for X in Xs):
-        for i, X in enumerate(Xs):
-            if X.shape[0] == 0:
-                fout[i].zero_()
+    out, fout = _lr_cells_run(Xs, ys, Ks, mean, sd, wb, keys, filters, True, max_slab_bytes, (precision, floats))
     return (out, fout) if floats else out
 
 

@@ -1,6 +1,6 @@
 """Logistic regression over SQL cohorts on the GPU: the cell plan
 (dx_group_cells, a stable sort) and the grouped fused encoder
-(dx_lr_encode_cells: the fp64-MFMA tile-block body with the rows read through
+(dx_lr_encode with a cell plan: the fp64-MFMA tile-block body with the rows read through
 the plan, a cell's record blocks one more factor of the grid) against the host
 model on exact inputs -- every sum is exact in fp64 in any order, so the
 comparison is ``torch.equal`` -- the anchors to the ungrouped encoder and the

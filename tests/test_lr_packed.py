@@ -109,6 +109,27 @@ def test_layout_agreement_k1():
     assert torch.equal(lr.encode_coefficients_int(X, y, packed_params(lp0)), lr.encode_coefficients_int(X, y, lp0))
 
 
+def test_slab_rule_is_the_two_drivers_rules():
+    """``native._lr_slab_uninit`` against the two expressions it replaced (the
+    batch driver's and the grouped driver's, copied here as they stood), on the
+    (upper plan, packed reader) combinations each driver reaches; a slab with
+    an unwritten record block is never left uninitialised."""
+    from drynx_amd import native as nt
+
+    for D in range(2, 121):
+        for T in (1, 2, 5, 64):
+            P = nt._lr_padded(D + T)
+            for upper in (False, True):  # the batch driver: the upper plan goes with the packed reader
+                assert nt._lr_slab_uninit(D, T, upper, upper, True) == \
+                    (upper or P == 48 or (D + 15) // 16 == P // 16), (D, T, upper)
+            for upper, packed in ((False, False), (True, True), (True, False)):  # the grouped driver
+                assert nt._lr_slab_uninit(D, T, upper, packed, True) == \
+                    ((upper and packed) or P == 48 or ((D + 15) // 16 == P // 16 and not upper)), (D, T, upper, packed)
+            for upper in (False, True):
+                for packed in (False, True):
+                    assert nt._lr_slab_uninit(D, T, upper, packed, False) is False
+
+
 def test_packed_query_cpu(tmp_path):
     w, clear, lp = run_packed_query("BC", "cpu", str(tmp_path / "p1"))
     assert len(clear) == hd.N_DPS and all(len(v) == 5252 for v in clear)

@@ -1,6 +1,6 @@
 """Distinct-coefficient packing on the GPU: the packed reducer
 (dx_lr_reduce_pack: block sum + upper-triangle gather + rounding in one
-launch), the encoder's upper launch plan (dx_lr_encode_upper), and
+launch), the encoder's upper launch plan (dx_lr_encode, upper), and
 Packing = 1 queries end to end.  A packed value must be the same bits as the
 cartesian path's value at (i, j), i <= j.  Run with -m gpu."""
 import pytest
@@ -70,6 +70,45 @@ def test_reduce_pack_hand_built_slab(gpu_device):
     assert got[1][:4] == [0, 2, 2, -2] and got[1][6] == 0 and got[1][8] == -3
     with pytest.raises(ValueError):
         nt.lr_reduce_pack(slab, 48, 1.0)  # row D = 48 is outside a 48 x 48 block
+
+
+def test_reducers_write_into_a_given_destination(gpu_device, monkeypatch):
+    """``out=`` / ``fout=``: rows 1..2 of a larger result hold exactly what the
+    reducers return for items 1..2, row 0 is untouched; a destination that is
+    not contiguous or of another shape is refused before any launch."""
+    D, T, L = 4, 2, 2 * 4 + 4 * 5 // 2
+    slab = torch.randn(3, 5, 48, 48, dtype=torch.float64, generator=_gen(11)).to(gpu_device)
+    exp, exp_f = nt.lr_reduce_pack(slab[1:3], D, 100.0, floats=True, T=T)
+    assert exp.shape == (2, L)
+    big = torch.full((3, L), -7, dtype=torch.int64, device=gpu_device)
+    fbig = torch.full((3, L), -7.0, dtype=torch.float64, device=gpu_device)
+    got, got_f = nt.lr_reduce_pack(slab[1:3], D, 100.0, floats=True, T=T, out=big[1:3], fout=fbig[1:3])
+    assert got.data_ptr() == big[1:3].data_ptr() and got_f.data_ptr() == fbig[1:3].data_ptr()
+    assert torch.equal(big[1:3], exp) and torch.equal(fbig[1:3].view(torch.int64), exp_f.view(torch.int64))
+    assert (big[0] == -7).all() and (fbig[0] == -7.0).all()
+    big.fill_(-7)
+    assert nt.lr_reduce_pack(slab[1:3], D, 100.0, T=T, out=big[1:3]).data_ptr() == big[1:3].data_ptr()
+    assert torch.equal(big[1:3], exp) and (big[0] == -7).all()
+    tot = nt.lr_reduce(slab[1:3])
+    tbig = torch.full((3, 48, 48), -7.0, dtype=torch.float64, device=gpu_device)
+    assert nt.lr_reduce(slab[1:3], out=tbig[1:3]).data_ptr() == tbig[1:3].data_ptr()
+    assert torch.equal(tbig[1:3].view(torch.int64), tot.view(torch.int64)) and (tbig[0] == -7.0).all()
+    # refused before any launch
+    calls = []
+    raw = nt._raw_call
+    monkeypatch.setattr(nt, "_raw_call", lambda name, *a: calls.append(name) or raw(name, *a))
+    wide = torch.zeros((2, 2 * L), dtype=torch.int64, device=gpu_device)
+    for bad in (wide[:, :L], big[:1], big[1:3].to(torch.int32)):
+        with pytest.raises(ValueError):
+            nt.lr_reduce_pack(slab[1:3], D, 100.0, T=T, out=bad)
+    for bad in (wide.to(torch.float64)[:, :L], fbig[:1]):
+        with pytest.raises(ValueError):
+            nt.lr_reduce_pack(slab[1:3], D, 100.0, floats=True, T=T, fout=bad)
+    twide = torch.zeros((2, 48, 96), dtype=torch.float64, device=gpu_device)
+    for bad in (twide[:, :, :48], tbig[:1], tbig[1:3].reshape(2, 48 * 48)):
+        with pytest.raises(ValueError):
+            nt.lr_reduce(slab[1:3], out=bad)
+    assert calls == []
 
 
 def _data(gpu_device, N, d):

@@ -1,5 +1,5 @@
 """Multi-target logistic regression on the GPU: the T-row encoder
-(dx_lr_encode_multi: level 1 of target t in row D + t of the fp64-MFMA
+(dx_lr_encode with T >= 2: level 1 of target t in row D + t of the fp64-MFMA
 output, one shared level 2), its upper launch plan, the T-aware packed
 reducer, and NbrTargets queries end to end.  Level-1 row t and all of level 2
 must be the same bits as the single-label encoder's on (X, Y[:, t]): per
@@ -92,28 +92,43 @@ def test_multi_packed_equals_cartesian(gpu_device, N, d, T):
                 assert torch.equal(lr.pack(vals, d, 2), got[0])
 
 
-def _launch_into(slab, X, Y, m, s, upper):
-    """dx_lr_encode_multi into a slab the caller filled: [nb, P, P]."""
-    N, dx = X.shape
-    T = Y.shape[1]
-    Yd = Y.to(torch.float64).contiguous()
-    assert slab.shape == (nt._lr_blocks(N), nt._lr_padded(dx + 1 + T), nt._lr_padded(dx + 1 + T))
-    _, st = nt._ctx(X)
-    rc = nt._raw_call("dx_lr_encode_multi", st, nt._ptr(X), X.stride(0), N, dx, nt._ptr(m), nt._ptr(s), nt._ptr(Yd),
-                      Yd.stride(0), T, -1.0, nt._ptr(slab), slab.shape[0], slab.shape[1], 1 if upper else 0)
-    assert rc == 0
+def _launch_into(slab, X, Y, m, s, upper, one_cell=False):
+    """The one encoder launch into a slab the caller filled: [nb, P, P].
+    ``one_cell``: the grouped kernels through the identity plan, one cell that
+    holds every record in order."""
+    N = X.shape[0]
+    p = nt._lr_prepare([X], [Y], m, s, 0.0)
+    assert slab.shape == (nt._lr_blocks(N), p.P, p.P)
+    cells = None
+    if one_cell:
+        cells = (torch.arange(N, device=X.device), torch.tensor([0, N], device=X.device), 0, nt._lr_blocks(N))
+    nt._lr_launch(p, X, nt._lr_labels(p, X, Y), 0.0, -1.0, slab, slab.shape[0], upper, cells)
     return slab
 
 
-# the wide shapes (P > 48) and which 48-row tile-blocks (Y, Z) the upper plan skips
+# the wide shapes (P > 48) and which 48-row tile-blocks (Y, Z) the upper plan skips; the last two: the single-label
+# kernels at the smallest shapes with a skipped tile-block and with a ragged edge
 @pytest.mark.parametrize("N,d,T,skipped", [(123, 44, 4, []), (70, 46, 2, []), (77, 47, 2, []), (64, 94, 2, []),
                                            (211, 100, 5, [(1, 0)]), (1, 100, 2, [(1, 0)]), (9, 2, 64, []),
-                                           (130, 150, 3, [(1, 0), (2, 0), (2, 1)])])
+                                           (130, 150, 3, [(1, 0), (2, 0), (2, 1)]),
+                                           (211, 100, 1, [(1, 0)]), (123, 44, 1, [])])
 def test_upper_plan_writes_what_the_packed_reducer_reads(gpu_device, N, d, T, skipped):
     """The slab pre-filled with NaN: the packed reducer's output has no NaN,
     so every element it reads is written and nothing skipped is read; the
     skipped tile-blocks (strictly below the diagonal, no row >= D) stay NaN,
     the padding column tiles too; everything written is the full plan's bits."""
+    _check_upper_plan(gpu_device, N, d, T, skipped, False)
+
+
+@pytest.mark.parametrize("N,d,T,skipped", [(211, 100, 1, [(1, 0)]), (211, 100, 5, [(1, 0)]), (123, 44, 4, [])])
+def test_upper_plan_of_the_grouped_kernels(gpu_device, N, d, T, skipped):
+    """The same through the grouped instantiations (one cell holding every
+    record in order), and each slab is the ungrouped one element for element
+    wherever either is written."""
+    _check_upper_plan(gpu_device, N, d, T, skipped, True)
+
+
+def _check_upper_plan(gpu_device, N, d, T, skipped, grouped):
     D = d + 1
     P = nt._lr_padded(D + T)
     X = (torch.rand(N, d, dtype=torch.float64, generator=_gen(N + d)) * 4).to(gpu_device)
@@ -122,8 +137,16 @@ def test_upper_plan_writes_what_the_packed_reducer_reads(gpu_device, N, d, T, sk
     s = torch.full((d,), 1.15, dtype=torch.float64, device=gpu_device)
     nb = nt._lr_blocks(N)
     nan = float("nan")
-    up = _launch_into(torch.full((nb, P, P), nan, dtype=torch.float64, device=gpu_device), X, Y, m, s, True)
-    full = _launch_into(torch.full((nb, P, P), nan, dtype=torch.float64, device=gpu_device), X, Y, m, s, False)
+
+    def launch(upper, one_cell):
+        return _launch_into(torch.full((nb, P, P), nan, dtype=torch.float64, device=gpu_device), X, Y, m, s, upper,
+                            one_cell)
+
+    up, full = launch(True, grouped), launch(False, grouped)
+    if grouped:
+        for mine, ungrouped in ((up, launch(True, False)), (full, launch(False, False))):
+            assert torch.equal(torch.isnan(mine), torch.isnan(ungrouped))
+            assert torch.equal(mine.nan_to_num(0.0), ungrouped.nan_to_num(0.0))
     got, got_f = nt.lr_reduce_pack(up, D, 100.0, floats=True, T=T)
     assert got.shape == (1, T * D + D * (D + 1) // 2) and not torch.isnan(got_f).any()
     ref, ref_f = nt.lr_reduce_pack(full, D, 100.0, floats=True, T=T)
