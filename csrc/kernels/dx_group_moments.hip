@@ -15,6 +15,9 @@
 //              outside [0, kcard_j) has no key and is DROPPED, as the
 //              histogram drops out-of-domain records.
 //
+// The rule (the terms, row_group and their checker) lives in group_terms.h,
+// which the grouped rounds of an iterative query (dx_iter_round.hip) share.
+//
 // No key column: one group.  A frequency count is the same reduction: the pair
 // list is the single pair (C, C) and the counted column is one more innermost
 // key column (x, QueryMin, R), so a (group, bin) cell is a group.
@@ -36,16 +39,17 @@
 // Host path: the same tiles on the thread pool, adding to the output with
 // relaxed atomic adds -- bit-identical to the device.
 #include "exec.h"
+#include "group_terms.h"
 
 namespace {
+using dx::GroupTerms;
+using dx::row_group;
+using dx::set_terms;
 constexpr int kRows = 64;
 constexpr int kMaxCols = 64;                                   // data columns (+ the constant one)
 constexpr int kMaxPairs = (kMaxCols + 1) * (kMaxCols + 2) / 2;  // 2145
 constexpr int kThreads = 256;
 constexpr int kMaxUnits = (kMaxPairs + kThreads - 1) / kThreads;
-constexpr int kMaxKeys = 5;  // 4 group-by columns and the counted column of a frequency count
-constexpr int kMaxFilters = 8;
-constexpr int64_t kMaxGroups = (int64_t)1 << 24;
 constexpr int kLdsPerCU = 160 * 1024;
 constexpr int kStageBytes = kRows * (kMaxCols + 2) * 8 + kRows * 4;  // widest staging area + the keys
 // cells of one launch: what half a CU's LDS leaves beside the widest staging
@@ -54,7 +58,7 @@ constexpr int kMaxCells = (kLdsPerCU / 2 - kStageBytes) / 8 / 256 * 256;  // 588
 static_assert(kMaxCells >= kMaxPairs, "one group of the widest pair list fits a window");
 static_assert(kMaxCells * 8 + kStageBytes <= kLdsPerCU / 2, "two workgroups per CU");
 
-struct GroupArgs {
+struct GroupArgs : GroupTerms {  // G groups: out is [n_dp][G][P], zeroed by the caller
   const int64_t *Z;
   int64_t ldz;
   int C;
@@ -64,35 +68,8 @@ struct GroupArgs {
   const int16_t *pairs;  // [P][2], column index C = constant 1
   int P;
   int L;  // row lanes per pair
-  int n_keys, n_filters;
-  int kcol[kMaxKeys];
-  int64_t koff[kMaxKeys], kcard[kMaxKeys];
-  int fcol[kMaxFilters];
-  int64_t fval[kMaxFilters];
-  int64_t G;   // groups of the query: out is [n_dp][G][P], zeroed by the caller
-  int64_t g0;  // the window [g0, g0 + gw)
-  int gw;
   int64_t *out;
 };
-
-// The window-relative group of the row whose key / filter columns are krow,
-// -1 if the row does not pass the filter, has no key or lies outside the window.
-__host__ __device__ inline int row_group(const GroupArgs &a, const int64_t *krow) {
-#pragma unroll
-  for (int f = 0; f < kMaxFilters; f++)
-    if (f < a.n_filters && krow[a.fcol[f]] != a.fval[f]) return -1;
-  uint64_t key = 0;
-#pragma unroll
-  for (int j = 0; j < kMaxKeys; j++) {
-    if (j < a.n_keys) {
-      const uint64_t v = (uint64_t)krow[a.kcol[j]] - (uint64_t)a.koff[j];
-      if (v >= (uint64_t)a.kcard[j]) return -1;
-      key = key * (uint64_t)a.kcard[j] + v;
-    }
-  }
-  const uint64_t rel = key - (uint64_t)a.g0;  // key < G <= 2^24
-  return rel < (uint64_t)a.gw ? (int)rel : -1;
-}
 
 // Row stride of the staging area in int64: odd, so the 64-bit reads of
 // consecutive rows fall into different banks.
@@ -196,30 +173,6 @@ extern "C" int dx_group_moments_max_cells() { return kMaxCells; }
 // [g0, g0 + gw).  Every count, cardinality, column index and the cell cap is
 // checked here: an argument that does not fit returns -2 and launches nothing.
 namespace {
-// The key and filter terms of a call into a: false if a count, a column index
-// or a cardinality does not fit (nothing of a is then to be used).
-bool set_terms(GroupArgs &a, int CK, const int64_t *keys, int n_keys, const int64_t *filters, int n_filters) {
-  if (n_keys < 0 || n_keys > kMaxKeys || n_filters < 0 || n_filters > kMaxFilters || CK < 0) return false;
-  int64_t G = 1;
-  for (int j = 0; j < n_keys; j++) {
-    const int64_t col = keys[3 * j], card = keys[3 * j + 2];
-    if (col < 0 || col >= CK || card < 1 || card > kMaxGroups) return false;
-    G *= card;
-    if (G > kMaxGroups) return false;
-    a.kcol[j] = (int)col;
-    a.koff[j] = keys[3 * j + 1];
-    a.kcard[j] = card;
-  }
-  for (int f = 0; f < n_filters; f++) {
-    const int64_t col = filters[2 * f];
-    if (col < 0 || col >= CK) return false;
-    a.fcol[f] = (int)col;
-    a.fval[f] = filters[2 * f + 1];
-  }
-  a.n_keys = n_keys, a.n_filters = n_filters, a.G = G;
-  return true;
-}
-
 // cell[i] = the group of row i among all G, G for a row that is dropped
 struct RowCells {
   GroupArgs a;  // g0 = 0, gw = G: the window is every group

@@ -44,7 +44,42 @@
 // The hand-off between the stages is the launch boundary: no global atomics,
 // no counters, no fences, no zeroed state.  Host path: the same two stages on
 // the thread pool.
+//
+// K14e (dx_iter_round_cells): the counts of a round per cell of a SQL WHERE /
+// GROUP BY, every cell under a prefix of its own (G simultaneous searches):
+//
+//     out[dp][g][d] = #{ rows i of DP dp : row_group(i) == g, qmin <= x_i <= qmax,
+//                        (x_i - qmin) div hi == prefix[g], d == ((x_i - qmin) div lo) mod b }
+//
+// row_group is K14d's membership rule, the very function (group_terms.h); x_i
+// is column xcol of the key matrix K [rows][CK], read in place through its row
+// stride.  GPU: one 256-thread workgroup per tile of the host-made plan, the
+// tile's rows streamed with coalesced 64-bit loads, a row's group computed
+// once.  The counters live in LDS, one 32-bit counter per (group of the
+// window, digit): a launch covers the window [g0, g0 + gw) of consecutive
+// groups with gw * b <= kMaxCounters and ignores rows whose group falls outside
+// it (the binding loops over the windows, as K14d's does).  kMaxCounters is
+// half of a CU's 160 KiB of LDS, so two workgroups stay resident; the LDS is
+// sized per launch, so a small window leaves room for more.  A counted row
+// costs one LDS atomic.  The window's prefixes are READ THROUGH THE CACHE, one
+// 64-bit load per row that has a group and lies in the domain: staged in LDS
+// they would take 8 bytes beside the 4 * b bytes of a group's counters and
+// halve the window at small bases, while the at most 80 KiB of a window's
+// prefixes are read-only, shared by every workgroup and stay in L2.  After a
+// barrier the non-zero counters go to the caller-zeroed out with one 64-bit
+// global (vector) atomic each, as in K14d: a per-tile slab of gw * b partials
+// would be larger than the records it summarises, so K14c's second stage does
+// not carry over; integer adds do not depend on the order of tiles or atomics,
+// and there is no global state beyond out.  The binding's tiles stream at least
+// min(min(G, gw) * b, 2048) rows, so zeroing and flushing never outweigh the
+// records, and a tile stays below 2^31 rows for the 32-bit counters.
+// Memory safety does not depend on the prefixes, which the entry cannot read on
+// the device: a prefix is only ever COMPARED with the quotient o div hi, and the
+// counter index is g * b + (q - (q div b) * b) with q = o div lo, inside
+// [0, gw * b) whatever the prefix holds.  Host path: the same tiles on the
+// thread pool, adding to out with relaxed atomic adds -- bit-identical.
 #include "exec.h"
+#include "group_terms.h"
 
 namespace {
 constexpr int kThreads = 256;
@@ -267,4 +302,106 @@ extern "C" int dx_iter_round(int on_gpu, void *stream, const int64_t *Z, int64_t
   if (kind == kKindCounts) return run_hist(on_gpu, stream, a, n_tiles, G);
   return kind == kKindMax ? run_extreme<true>(on_gpu, stream, a, n_tiles, G)
                           : run_extreme<false>(on_gpu, stream, a, n_tiles, G);
+}
+
+// ---------------------------------------------------------------- cells (K14e)
+namespace {
+constexpr int kLdsPerCU = 160 * 1024;
+constexpr int kMaxCounters = kLdsPerCU / 2 / 4;  // 20480 32-bit counters of one launch
+constexpr int64_t kMaxCellOutputs = (int64_t)1 << 20;  // G * b of a query (rounds.ITER_MAX_CELL_OUTPUTS)
+static_assert(kMaxCounters >= kMaxHistBase, "one group of the largest base fits a window");
+static_assert(kMaxCounters * 4 <= kLdsPerCU / 2, "two workgroups per CU");
+
+struct CellArgs : dx::GroupTerms {  // G groups: out is [n_dp][G][base], zeroed by the caller
+  const int64_t *K;
+  int64_t ldk;
+  int xcol;
+  const int64_t *tiles;   // [n_tiles][3] = (dp, row0, row1)
+  const int64_t *prefix;  // [G], in the memory K lives in; never trusted
+  int64_t qmin, qmax, base, lo;
+  int64_t *out;
+};
+
+// The counter (window-relative group * base + digit) of the row whose columns
+// are krow, -1 if the row does not count.
+__host__ __device__ inline int cell_counter(const CellArgs &a, const int64_t *krow) {
+  const int g = dx::row_group(a, krow);
+  if (g < 0) return -1;
+  const int64_t x = krow[a.xcol];
+  if (x < a.qmin || x > a.qmax) return -1;
+  const uint64_t q = ((uint64_t)x - (uint64_t)a.qmin) / (uint64_t)a.lo;  // o div lo
+  const uint64_t p = q / (uint64_t)a.base;                                // o div hi, hi = lo * b
+  if ((int64_t)p != a.prefix[a.g0 + g]) return -1;                        // p < 2^40: a compare, no arithmetic
+  return g * (int)a.base + (int)(q - p * (uint64_t)a.base);
+}
+
+__global__ void __launch_bounds__(kThreads) cell_hist_kernel(CellArgs a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned int cell_cnt[];  // [gw][base]
+  const int n = a.gw * (int)a.base;
+  for (int i = threadIdx.x; i < n; i += kThreads) cell_cnt[i] = 0;
+  __syncthreads();
+  const int64_t dp = a.tiles[3 * (int64_t)blockIdx.x], r0 = a.tiles[3 * (int64_t)blockIdx.x + 1],
+                r1 = a.tiles[3 * (int64_t)blockIdx.x + 2];
+  for (int64_t r = r0 + threadIdx.x; r < r1; r += kThreads) {
+    const int c = cell_counter(a, a.K + r * a.ldk);
+    if (c >= 0) atomicAdd(&cell_cnt[c], 1u);
+  }
+  __syncthreads();
+  unsigned long long *o = reinterpret_cast<unsigned long long *>(a.out) + (dp * a.G + a.g0) * a.base;
+  for (int i = threadIdx.x; i < n; i += kThreads)
+    if (cell_cnt[i]) atomicAdd(o + i, (unsigned long long)cell_cnt[i]);
+}
+
+void host_cell_hist(const CellArgs &a, int64_t n_tiles) {
+  dx::host_for_each(n_tiles, [=](int64_t t) {
+    const int64_t dp = a.tiles[3 * t], r0 = a.tiles[3 * t + 1], r1 = a.tiles[3 * t + 2];
+    uint64_t *o = reinterpret_cast<uint64_t *>(a.out) + (dp * a.G + a.g0) * a.base;
+    for (int64_t r = r0; r < r1; r++) {
+      const int c = cell_counter(a, a.K + r * a.ldk);
+      if (c >= 0) __atomic_fetch_add(o + c, (uint64_t)1, __ATOMIC_RELAXED);
+    }
+  });
+}
+}  // namespace
+
+extern "C" int dx_iter_round_max_counters() { return kMaxCounters; }
+
+// One window of the grouped counts of a round.  keys [n_keys][3] and filters
+// [n_filters][2] are K14d's HOST arrays over K [rows][CK] (at most 4 keys: the
+// counted column xcol is not one of them), prefix [G] lives with K.  out
+// [n_dp][G][base] is zeroed by the caller before the first window; this call
+// adds the groups [g0, g0 + gw).  lo is b^(L-1-k) of round k, as dx_iter_round
+// takes it.  Everything that can be checked without reading device memory is
+// checked here -- the terms (the shared checker), xcol, the round, G * base, the
+// window, the counts, and on a host plan the tile length the 32-bit counters
+// allow: an argument that does not fit returns -2 and launches nothing.
+extern "C" int dx_iter_round_cells(int on_gpu, void *stream, const int64_t *K, int64_t ldk, int CK, int64_t xcol,
+                                   const int64_t *tiles, int64_t n_tiles, const int64_t *keys, int n_keys,
+                                   const int64_t *filters, int n_filters, int64_t qmin, int64_t qmax, int64_t base,
+                                   int64_t lo, const int64_t *prefix, int64_t g0, int64_t gw, int64_t *out) {
+  CellArgs a{};
+  if (n_keys >= dx::kMaxKeys || !dx::set_terms(a, CK, keys, n_keys, filters, n_filters)) return -2;
+  if (xcol < 0 || xcol >= CK) return -2;
+  if (!is_round(kKindCounts, n_tiles, 0, qmin, qmax, base, lo, 0)) return -2;
+  if (a.G * base > kMaxCellOutputs) return -2;
+  if (g0 < 0 || gw < 1 || g0 + gw > a.G || gw * base > kMaxCounters) return -2;
+  if (!on_gpu)
+    for (int64_t t = 0; t < n_tiles; t++)
+      if (tiles[3 * t + 2] - tiles[3 * t + 1] > 0x7fffffff) return -2;
+  if (n_tiles == 0) return 0;
+  a.K = K, a.ldk = ldk, a.xcol = (int)xcol, a.tiles = tiles, a.prefix = prefix;
+  a.qmin = qmin, a.qmax = qmax, a.base = base, a.lo = lo, a.g0 = g0, a.gw = (int)gw, a.out = out;
+  if (!on_gpu) {
+    host_cell_hist(a, n_tiles);
+    return 0;
+  }
+  const size_t bytes = (size_t)gw * (size_t)base * 4;
+  // the LDS limit of the kernel is raised once, to the largest window, not per launch
+  static const int lds_rc = dx::check_hip(
+      hipFuncSetAttribute(reinterpret_cast<const void *>(cell_hist_kernel),
+                          hipFuncAttributeMaxDynamicSharedMemorySize, kMaxCounters * 4),
+      "iter_round_cells (LDS size)");
+  if (lds_rc) return lds_rc;
+  hipLaunchKernelGGL(cell_hist_kernel, dim3((unsigned)n_tiles), dim3(kThreads), bytes, (hipStream_t)stream, a);
+  return dx::check_hip(hipGetLastError(), "iter_round_cells");
 }

@@ -142,6 +142,8 @@ _SIGS = {
     "dx_rp_coeffs": [_P, _P, _P, _L],
     "dx_int_moments": [_I, _P, _P, _L, _I, _P, _L, _P, _I, _P, _P],
     "dx_iter_round": [_I, _P, _P, _L, _P, _L, _P, _L, _I, _L, _L, _L, _L, _L, _P, _P],
+    "dx_iter_round_cells": [_I, _P, _P, _L, _I, _L, _P, _L, _P, _I, _P, _I, _L, _L, _L, _L, _P, _L, _L, _P],
+    "dx_iter_round_max_counters": [],
     "dx_group_moments": [_I, _P, _P, _L, _I, _P, _L, _I, _P, _L, _P, _I, _P, _I, _P, _I, _L, _L, _P],
     "dx_group_moments_max_cells": [],
     "dx_group_cells": [_I, _P, _P, _L, _I, _L, _P, _I, _P, _I, _P],
@@ -1317,6 +1319,89 @@ def iter_round(name: str, Z: torch.Tensor, seg_rows, qmin: int, qmax: int, base:
           _ptr(desc[: 3 * n_tiles]), n_tiles, _ptr(desc[3 * n_tiles:]), G, _ITER_KINDS[name], qmin, qmax, base, lo,
           prefix, _ptr(partial), _ptr(out))
     return out
+
+
+def rows_of_counts(name: str, cnt: torch.Tensor) -> torch.Tensor:
+    """The rows of a counting operation from the counts ``cnt`` [n_dp, ng, n]
+    of its bins, on their device: the one-shot SQL encoder's bins
+    (``ops.encoding.batch_values_sql``) and the digits of a grouped iterative
+    round (``iter_round_cells``)."""
+    if name == "frequencyCount":
+        return cnt
+    occ = (cnt > 0).to(torch.int64)
+    if name == "union":
+        return occ
+    if name == "inter":
+        return 1 - occ
+    if name == "min":  # an occupied bin at or below i
+        return (occ.cumsum(2) > 0).to(torch.int64)
+    if name != "max":
+        raise ValueError(f"{name} is not derived from counts")
+    return ((occ.flip(2).cumsum(2).flip(2) - occ) > 0).to(torch.int64)  # max: an occupied bin above i
+
+
+# LDS counters (group of the window x digit) of one launch of the grouped rounds: half a CU's 160 KiB
+# (csrc/kernels/dx_iter_round.hip kMaxCounters, exported as dx_iter_round_max_counters)
+ITER_ROUND_MAX_COUNTERS = 20480
+
+
+def iter_round_cells(name: str, K: torch.Tensor, seg_rows, xcol: int, qmin: int, qmax: int, base: int, round: int,
+                     prefixes, keys=(), filters=()) -> torch.Tensor:
+    """K14e (csrc/kernels/dx_iter_round.hip, dx_iter_round_cells): the [n_dp, G,
+    base] int64 rows every DP of a batch encrypts in round ``round`` of G
+    simultaneous iterative ``name`` searches, one per cell of a WHERE / GROUP BY.
+
+    K [rows, CK] int64 holds the DPs' record tables back to back (``seg_rows[d]``
+    rows for DP d) and is read in place through its row stride; ``keys`` and
+    ``filters`` are ``group_moments``' (at most 4 keys), G the product of the
+    cardinalities, and column ``xcol`` of K is the counted one.  Cell g counts
+    the rows of its group (``group_moments``' membership rule, the same
+    function) with x inside [qmin, qmax] and (x - qmin) div base^(L-round) ==
+    ``prefixes[g]`` by their digit ((x - qmin) div base^(L-1-round)) mod base
+    (``rounds.iter_round_cells``; ``len(prefixes) == G``); records outside the
+    domain are dropped.  min / max: the unary rows of the first / last occupied
+    digit, derived from the counts on the device as ``batch_values_sql`` derives
+    the one-shot rows ([an occupied digit at or below i] / [one above i]); a
+    cell without a record under its prefix gives the all-zero row.
+
+    One launch per window of ``ITER_ROUND_MAX_COUNTERS // base`` consecutive
+    groups (the counters of a window live in LDS), one upload for the plan and
+    one for the prefixes, no torch op and no host work per record."""
+    assert K.dtype == torch.int64 and K.dim() == 2
+    qmin, qmax, base, xcol = int(qmin), int(qmax), int(base), int(xcol)
+    what = f"iterative {name} over cells"
+    keys, filters, CK, G = _group_terms(what, K, K.shape[0], "K", keys, filters)
+    prefixes = [int(p) for p in prefixes]
+    _, lo = rounds.iter_round_cells(name, qmin, qmax, base, round, prefixes, G)
+    if not 0 <= xcol < CK:
+        raise ValueError(f"{what}: column {xcol} of a {CK}-column key matrix")
+    counts = np.asarray(seg_rows, dtype=np.int64).reshape(-1)
+    n_dp = len(counts)
+    if counts.sum() != K.shape[0] or (n_dp and counts.min() < 0):
+        raise ValueError(f"{what}: segments cover {counts.sum()} rows, K has {K.shape[0]}")
+    out = torch.zeros((n_dp, G, base), dtype=torch.int64, device=K.device)
+    gw = max(1, ITER_ROUND_MAX_COUNTERS // base)
+    # a tile zeroes and flushes its window's counters: it streams at least as many rows
+    plan, _ = _tile_plan(counts, min(min(G, gw) * base, 2048))
+    n_tiles = len(plan)
+    if n_tiles == 0:
+        return rows_of_counts(name, out)
+    if int((plan[:, 2] - plan[:, 1]).max()) >= 1 << 31:
+        raise ValueError(f"{what}: a tile of 2^31 rows or more")
+    tiles = _upload(plan, K.device)
+    pre = _upload(np.asarray(prefixes, dtype=np.int64), K.device)
+    kd = np.ascontiguousarray(np.asarray(keys, dtype=np.int64).reshape(-1))
+    fd = np.ascontiguousarray(np.asarray(filters, dtype=np.int64).reshape(-1))
+    g, s = _ctx(K)
+    for g0 in range(0, G, gw):
+        rc = _raw_call("dx_iter_round_cells", g, s, _ptr(K, strided=True), K.stride(0), CK, xcol, _ptr(tiles),
+                       n_tiles, kd.ctypes.data_as(_P), len(keys), fd.ctypes.data_as(_P), len(filters), qmin, qmax,
+                       base, lo, _ptr(pre), g0, min(gw, G - g0), _ptr(out))
+        if rc == -2:
+            raise ValueError(f"{what}: the entry refused its arguments")
+        if rc != 0:
+            raise RuntimeError(f"native op dx_iter_round_cells failed (rc={rc})")
+    return rows_of_counts(name, out)
 
 
 def sha256_rows(data: torch.Tensor, chunk: int) -> torch.Tensor:

@@ -259,16 +259,7 @@ def batch_values_sql(name: str, Z: torch.Tensor, K: torch.Tensor, seg_rows, sql_
     n = qmax - qmin + 1
     cnt = nt.group_moments(Z[:, :0], K, seg_rows, [(0, 0)], keys, filters, bins=(sql_plan.select[0], qmin, n))
     cnt = cnt.reshape(len(seg_rows), -1, n)
-    if name == "frequencyCount":
-        return cnt
-    occ = (cnt > 0).to(torch.int64)
-    if name == "union":
-        return occ
-    if name == "inter":
-        return 1 - occ
-    if name == "min":  # an occupied bin at or below i
-        return (occ.cumsum(2) > 0).to(torch.int64)
-    return ((occ.flip(2).cumsum(2).flip(2) - occ) > 0).to(torch.int64)  # max: an occupied bin above i
+    return nt.rows_of_counts(name, cnt)
 
 
 def iterative_values(operation: Operation, Z: torch.Tensor, seg_rows, base: int, rnd: int, prefix: int):
@@ -287,6 +278,32 @@ def iterative_values(operation: Operation, Z: torch.Tensor, seg_rows, base: int,
     if operation.NameOp not in ITER_OPERATIONS:
         raise ValueError(f"{operation.NameOp} has no iterative rounds")
     return nt.iter_round(operation.NameOp, Z, seg_rows, operation.QueryMin, operation.QueryMax, base, rnd, prefix)
+
+
+def iterative_values_sql(operation: Operation, K: torch.Tensor, seg_rows, plan, base: int, rnd: int, prefixes):
+    """[n_dp, G, base] int64 values of one round of an iterative query with
+    ``Query.SQL``: G simultaneous searches, one per cell of ``plan``
+    (``query.SQLPlan``) in ``all_possible_groups`` order, cell g under
+    ``prefixes[g]``.  K [rows, width] stacks the DPs' record tables; a cell's
+    records are the rows that pass the WHERE conjunction and carry its key
+    digits (``batch_values_sql``'s rule), with the counted column
+    ``plan.select[0]`` inside the domain and under the cell's prefix.
+    frequencyCount: the digit's counts; min / max: [an occupied digit at or
+    below i] / [an occupied digit above i], all zero for a cell with no record
+    under its prefix.  For honest DPs this is the ungrouped rule of
+    ``iterative_values`` ("the DP's clamped extreme lies under the prefix")
+    without the clamping: records outside the domain are DROPPED, as
+    ``batch_values_sql`` drops them, and no record can lie below the prefix of
+    the global minimum (above that of the maximum), so a DP's first (last)
+    occupied digit under the prefix is the digit of its extreme.  One launch
+    per group window for every DP (``native.iter_round_cells``)."""
+    from .. import native as nt
+
+    if operation.NameOp not in ITER_OPERATIONS:
+        raise ValueError(f"{operation.NameOp} has no iterative rounds")
+    keys = [(c, 0, v) for c, v in plan.group_by]
+    return nt.iter_round_cells(operation.NameOp, K, seg_rows, plan.select[0], operation.QueryMin, operation.QueryMax,
+                               base, rnd, prefixes, keys, list(plan.where))
 
 
 def encode_iterative(data, operation: Operation, base: int, rnd: int, prefix: int, pk, with_proofs=False,

@@ -199,7 +199,9 @@ def dp_encode_batch(ctx, sq, dps: list) -> dict:
             Z = Z.pin_memory().to(device, non_blocking=True)
     else:
         Z = torch.cat([m.to(device) for m in mats]).contiguous()
-    if plan is not None:  # WHERE / GROUP BY: [n_dp, ng, n_out] from K14d, the table its key and filter columns
+    if plan is not None and sq.IterBase:  # one round of a search per cell: [n_dp, ng, IterBase] from K14e
+        vals = enc.iterative_values_sql(op, Z, rows, plan, sq.IterBase, sq.IterRound, sq.IterPrefixes)
+    elif plan is not None:  # WHERE / GROUP BY: [n_dp, ng, n_out] from K14d, the table its key and filter columns
         sel = plan.select
         Zv = Z[:, sel[0]: sel[0] + len(sel)] if sel == list(range(sel[0], sel[0] + len(sel))) else Z[:, sel]
         vals = enc.batch_values_sql(op.NameOp, Zv, Z, rows, plan, op.QueryMin, op.QueryMax)

@@ -18,7 +18,8 @@ from dataclasses import dataclass, field, fields, is_dataclass
 from typing import Optional
 
 from .crypto import oracle as O
-from .rounds import ITER_MAX_BASE, ITER_MAX_HIST_BASE, ITER_MAX_RANGE, ITER_OPERATIONS, iter_rounds  # re-exported
+from .rounds import (ITER_MAX_BASE, ITER_MAX_CELL_OUTPUTS, ITER_MAX_HIST_BASE, ITER_MAX_RANGE,  # re-exported
+                     ITER_OPERATIONS, iter_rounds)
 from .utils.log import get_logger
 
 log = get_logger("query")
@@ -182,7 +183,11 @@ class QuerySQL:
       of its float features; ``Select`` must stay empty; LRParameters has K = 2
       (level 2's first entry carries the cell's record count, with which the
       querier descends) and global Means and StandardDeviations; an empty cell
-      decodes to NaN weights.
+      decodes to NaN weights;
+    * iterative rounds (``SurveyQuery.IterBase`` with ``min``, ``max`` or
+      ``frequencyCount``): one search per cell, cell g under
+      ``SurveyQuery.IterPrefixes[g]``; a cell's records are those of its group
+      that pass ``Where``, lie in [QueryMin, QueryMax] and under its prefix.
 
     All empty = the query without SQL, in every respect."""
     Select: list = field(default_factory=list)
@@ -322,10 +327,20 @@ class SurveyQuery:
     # A frequencyCount round (the rounds of a quantile search) answers with the
     # b counts of that digit among the DP's in-domain records under the prefix
     # (the same kernel file).
+    # With a non-empty Query.SQL the round is one round of G simultaneous
+    # searches, one per cell of the SQL plan (G = the product of the GROUP BY
+    # cardinalities, 1 with WHERE only; cells in all_possible_groups order):
+    # IterPrefix stays 0 and IterPrefixes[g] is cell g's prefix, exactly G
+    # entries in every round, all zero in round 0.  Cell g's answer is the
+    # round's b values over the records of its group that pass the WHERE
+    # conjunction, lie in the domain and under IterPrefixes[g]; min / max are the
+    # unary rows of the first / last occupied digit (all zero without a record).
+    # Without SQL the list is empty, and an empty list is not sent.
     IterBase: int = 0
     IterRound: int = 0
     IterPrefix: int = 0
     IterSurveyID: str = ""
+    IterPrefixes: list = field(default_factory=list)
 
     # -------------------------------------------------------------- helpers
     def all_dps(self):
@@ -383,6 +398,8 @@ def _to_jsonable(obj):
                 out[f.name] = None if v is None else [[s.to_dict() for s in row] for row in v]
             elif isinstance(v, QuerySQL) and not v:
                 continue  # an empty SQL is the dict of a query without the field
+            elif f.name == "IterPrefixes" and not v:
+                continue  # likewise: the dict of every survey without cell prefixes is unchanged
             else:
                 out[f.name] = _to_jsonable(v)
         return out
@@ -443,6 +460,7 @@ def _survey_from_dict(d: dict) -> SurveyQuery:
         IterRound=d.get("IterRound", 0),
         IterPrefix=d.get("IterPrefix", 0),
         IterSurveyID=d.get("IterSurveyID", ""),
+        IterPrefixes=list(d.get("IterPrefixes") or []),
     )
 
 
@@ -531,15 +549,18 @@ def check_parameters(sq: SurveyQuery, diffp: bool) -> bool:
 def _check_iterative(sq: SurveyQuery) -> list:
     """Rules of the iterative min/max extension (IterBase > 0); nothing when it is off."""
     b = sq.IterBase
+    q = sq.Query
     if b == 0:
-        if sq.IterRound or sq.IterPrefix:
+        if sq.IterRound or sq.IterPrefix or sq.IterPrefixes:
             return ["iterative round or prefix without a base"]
         return []
-    q = sq.Query
+    if sq.IterPrefixes and not q.SQL:
+        return ["iterative cell prefixes (IterPrefixes) without a SQL part"]
     op = q.Operation
     msg = []
     hist = op.NameOp == "frequencyCount"
-    top = ITER_MAX_HIST_BASE if hist else ITER_MAX_BASE
+    # (over SQL cells every operation is derived from the digit's counts)
+    top = ITER_MAX_HIST_BASE if hist or q.SQL else ITER_MAX_BASE
     if not isinstance(b, int) or isinstance(b, bool) or not 2 <= b <= top:
         return [f"iterative base outside 2..{top}"]
     if op.NameOp not in ITER_OPERATIONS:
@@ -594,15 +615,55 @@ def _check_sql(sq: SurveyQuery) -> list:
                        "standardisation is global; one per cell is not defined)")
     elif name not in SQL_OPERATIONS:
         msg.append(f"SQL with the operation {name}")
-    if sq.IterBase:
-        msg.append("SQL with iterative rounds")
+    if sq.IterBase and name not in ITER_OPERATIONS:
+        msg.append("SQL with iterative rounds")  # no operation with rounds: there are no searches per cell
     if q.CuttingFactor != 0:
         msg.append("SQL with a cutting factor")
     try:
-        sql_plan(q)
+        plan = sql_plan(q)
     except ValueError as e:
         msg.append(str(e))
+        return msg
+    if sq.IterBase and name in ITER_OPERATIONS:
+        bad = _check_cell_prefixes(sq, plan)
+        if bad:
+            msg.append(f"SQL with iterative rounds: {bad}")
     return msg
+
+
+def sql_cells(plan: SQLPlan) -> int:
+    """G, the cells of a SQL plan: the product of the GROUP BY cardinalities, 1 with WHERE only."""
+    G = 1
+    for _, v in plan.group_by:
+        G *= v
+    return G
+
+
+def _check_cell_prefixes(sq: SurveyQuery, plan: SQLPlan) -> str:
+    """The violated rule of a round of G simultaneous searches (SQL with
+    IterBase), "" when there is none; the base, the round and the domain are
+    ``_check_iterative``'s to refuse."""
+    b, k, G = sq.IterBase, sq.IterRound, sql_cells(plan)
+    if not isinstance(b, int) or isinstance(b, bool) or not 2 <= b <= ITER_MAX_HIST_BASE:
+        return ""
+    if G * b > ITER_MAX_CELL_OUTPUTS:
+        return f"{G} cells of {b} outputs (at most {ITER_MAX_CELL_OUTPUTS})"
+    if sq.IterPrefix != 0:
+        return "IterPrefix must stay 0, the cells' prefixes travel in IterPrefixes"
+    ps = sq.IterPrefixes
+    if not isinstance(ps, (list, tuple)) or len(ps) != G:
+        return f"IterPrefixes needs one entry per cell ({G})"
+    # the power below is taken for a round of the domain only: IterRound comes off the wire
+    op = sq.Query.Operation
+    if not 1 <= op.QueryMax - op.QueryMin + 1 <= ITER_MAX_RANGE:
+        return ""
+    if not isinstance(k, int) or isinstance(k, bool) or not 0 <= k < iter_rounds(op.QueryMin, op.QueryMax, b):
+        return ""
+    top = b ** k
+    if any(not isinstance(p, int) or isinstance(p, bool) or not 0 <= p < top for p in ps):
+        return "an entry of IterPrefixes is not a number of IterRound digits" if k else \
+            "IterPrefixes must be all zero in round 0"
+    return ""
 
 
 def query_to_proofs_nbrs(sq: SurveyQuery) -> list:

@@ -15,6 +15,10 @@ ITER_OPERATIONS = ("min", "max", "frequencyCount")
 ITER_MAX_BASE = 65536
 ITER_MAX_HIST_BASE = 4096  # frequencyCount rounds: one LDS counter per output (csrc/kernels/dx_iter_round.hip)
 ITER_MAX_RANGE = 1 << 40  # every power of the base a round divides by stays far inside int64
+# rounds over the G cells of a SQL plan (one search per cell, SurveyQuery.IterPrefixes): G * base outputs per DP
+# (csrc/kernels/dx_iter_round.hip dx_iter_round_cells checks the same number); every operation counts, so the
+# base is at most ITER_MAX_HIST_BASE
+ITER_MAX_CELL_OUTPUTS = 1 << 20
 
 
 def max_base(name: str) -> int:
@@ -51,3 +55,22 @@ def iter_round(name: str, qmin: int, qmax: int, base: int, k: int, prefix: int) 
     if not 0 <= k < L or not 0 <= prefix < base ** k:
         raise ValueError(f"iterative {name}: round {k} of {L}, prefix {prefix}")
     return L, base ** (L - 1 - k)
+
+
+def iter_round_cells(name: str, qmin: int, qmax: int, base: int, k: int, prefixes, n_cells: int) -> tuple:
+    """``(L, lo)`` of round ``k`` of ``n_cells`` simultaneous iterative ``name``
+    searches, one per cell of a SQL plan, cell g under ``prefixes[g]``: the
+    round of ``iter_round`` with the counting base limit (min / max are derived
+    from the counts) for every distinct prefix, exactly ``n_cells`` prefixes
+    and ``n_cells * base`` at most ITER_MAX_CELL_OUTPUTS."""
+    if name not in ITER_OPERATIONS:
+        raise ValueError(f"Operation: <{name}> has no iterative rounds")
+    prefixes = [int(p) for p in prefixes]
+    if n_cells < 1 or len(prefixes) != n_cells:
+        raise ValueError(f"iterative {name}: {len(prefixes)} prefixes for {n_cells} cells")
+    if n_cells * int(base) > ITER_MAX_CELL_OUTPUTS:
+        raise ValueError(f"iterative {name}: {n_cells} cells of {base} outputs (at most {ITER_MAX_CELL_OUTPUTS})")
+    out = None
+    for p in sorted(set(prefixes)):
+        out = iter_round("frequencyCount", qmin, qmax, base, k, p)
+    return out

@@ -17,7 +17,7 @@ import copy
 from ..crypto import elgamal as eg
 from ..ops import encoding as enc
 from ..query import (LogisticRegressionParameters, Operation, Query, QueryDiffP, QueryDPDataGen, QueryIVSigs, Roster,
-                     SurveyQuery, check_parameters, iter_operation, iter_rounds, new_survey_id)
+                     SurveyQuery, check_parameters, iter_operation, iter_rounds, new_survey_id, sql_cells, sql_plan)
 from ..utils import timers
 
 
@@ -107,8 +107,10 @@ class DrynxClient:
         return enc.decode(cv, self.keypair.secret, op, self.table)
 
     # ------------------------------------------------------------------ iterative min / max
-    def iterative_round_query(self, sq: SurveyQuery, base: int, k: int, prefix: int, iter_id: str) -> SurveyQuery:
-        """Round ``k`` of the iterative search ``iter_id`` as a survey of its own:
+    def iterative_round_query(self, sq: SurveyQuery, base: int, k: int, prefix, iter_id: str) -> SurveyQuery:
+        """Round ``k`` of the iterative search ``iter_id`` as a survey of its own
+        (``prefix``: the digits found so far, or for a survey with SQL the list of
+        them, one per cell, which travels as IterPrefixes):
         a copy of ``sq`` (a ``min``/``max``/``frequencyCount`` survey over the full
         domain) with ``base`` outputs, the first ``base`` columns of its ranges and
         input-validation signatures (the same objects every round, so the
@@ -129,6 +131,8 @@ class DrynxClient:
                 raise ValueError(f"input-validation signatures for fewer than {base} outputs per round")
             cut = self._iter_columns(sigs, base, per_cn=True)
             q.IVSigs = QueryIVSigs(InputValidationSigs=cut, InputValidationSize1=len(cut), InputValidationSize2=base)
+        if sq.Query.SQL:
+            prefix, rq.IterPrefixes = 0, [int(p) for p in (prefix if isinstance(prefix, (list, tuple)) else [prefix])]
         rq.IterBase, rq.IterRound, rq.IterPrefix, rq.IterSurveyID = int(base), int(k), int(prefix), iter_id
         rq.SurveyID = f"{iter_id}.r{k}"  # no '/': ledger buckets and proof keys are '<survey id>/<kind>/...'
         return rq
@@ -151,38 +155,65 @@ class DrynxClient:
         memo[(id(cols), base)] = (cols, cut)
         return cut
 
+    @staticmethod
+    def _iter_cells(sq: SurveyQuery):
+        """The searches one walk over ``sq`` carries: None without SQL (one, its
+        prefix travels as IterPrefix), with SQL the cells G of its plan (their
+        prefixes travel as IterPrefixes; 1 with WHERE only)."""
+        plan = sql_plan(sq.Query)
+        return None if plan is None else sql_cells(plan)
+
     def _iterative_walk(self, sq: SurveyQuery, base: int, what: str, decoder, rule, on_round):
-        """The rounds of one iterative search over ``sq``: round k's query carries
-        the k digits found so far, ``decoder`` turns its aggregate into
-        ``client_out`` (one entry per group) and ``rule(k, prefix, client_out)``
-        into ``(digit, failed, empty)``: the round's digit, a message when the
-        answers contradict an earlier round or each other, or that there is
-        nothing to search.  Returns ``(prefix, empty, rounds, iter_id)``;
-        raises the first failure."""
+        """The rounds of one iterative search over ``sq``, or with SQL of the G
+        searches of its cells side by side: round k's query carries the k
+        digits found so far for every search (a list of prefixes, of length 1
+        without SQL), ``decoder`` turns its aggregate into ``client_out`` (one
+        entry per group) and ``rule(k, prefixes, client_out)`` into ``(digits,
+        failed, empty)``: the round's digit of every search, a message when
+        the answers contradict an earlier round or each other, or that there
+        is nothing to search.  One ``run_survey`` per round, L rounds for every
+        cell.  Returns ``(prefixes, empty, rounds, iter_id)``; raises the first
+        failure.  ``on_round`` gets the digit without SQL, the list with."""
         op = sq.Query.Operation
         L = iter_rounds(op.QueryMin, op.QueryMax, base)
         iter_id = sq.SurveyID or new_survey_id()
         collective = getattr(getattr(self.entry, "comm", None), "world", 1) > 1
+        cells = self._iter_cells(sq)
+        n = 1 if cells is None else cells
         # With several ranks the others serve exactly L rounds (``serve_iterative``):
         # a search that has failed, or found nothing to search, still runs them all.
-        prefix, rounds, failed, empty = 0, [], None, False
+        prefixes, rounds, failed, empty = [0] * n, [], None, False
         for k in range(L):
-            rq = self.iterative_round_query(sq, base, k, prefix, iter_id)
+            rq = self.iterative_round_query(sq, base, k, prefixes[0] if cells is None else prefixes, iter_id)
             if k == 0 and not check_parameters(rq, False):
                 raise ValueError("the iterative query fails CheckParameters")
             res = self.entry.run_survey(rq, on_result=decoder)
             rounds.append(res)
-            digit = 0
+            digits = [0] * n
             if failed is None and not empty:
-                digit, failed, empty = rule(k, prefix, res.client_out)
+                digits, failed, empty = rule(k, prefixes, res.client_out)
             if (failed is not None or empty) and not collective:
                 break
             if on_round is not None:
-                on_round(k, digit, res)
-            prefix = prefix * base + digit
+                on_round(k, digits[0] if cells is None else list(digits), res)
+            prefixes = [p * base + d for p, d in zip(prefixes, digits)]
         if failed is not None:
             raise RuntimeError(f"iterative {what} {iter_id}: {failed}")
-        return prefix, empty, rounds, iter_id
+        return prefixes, empty, rounds, iter_id
+
+    @staticmethod
+    def _cell_outs(k: int, cells: int, outs: list):
+        """``(one decoded entry per cell, failure)`` of a round's ``client_out``:
+        with GROUP BY the ciphertext groups are the cells; with WHERE only
+        the one cell's answer is replicated over the groups of GroupByValues,
+        which must agree."""
+        if cells == 1:
+            if any(x != outs[0] for x in outs):
+                return None, f"round {k}: the groups disagree on the one cell's answer"
+            return outs[:1], None
+        if len(outs) != cells:
+            return None, f"round {k}: {len(outs)} groups answered for {cells} cells"
+        return outs, None
 
     def send_iterative_extreme(self, sq: SurveyQuery, base: int, on_round=None):
         """Iterative min/max (extension): the result of the ``min``/``max`` survey
@@ -193,7 +224,15 @@ class DrynxClient:
         far in clear.  Returns ``(value, rounds)``: the decoded extreme and
         every round's SurveyResult.  ``on_round(k, digit, result)`` is called
         after each round.  Raises when the DPs' answers contradict an earlier
-        round (a ``min`` round nobody matches) or the groups disagree."""
+        round (a ``min`` round nobody matches) or the groups disagree.
+
+        A survey with SQL: one search per cell of its WHERE / GROUP BY, all in
+        the same L rounds (``SurveyQuery.IterPrefixes``).  Returns ``([value per
+        cell], rounds)``, a list of one with WHERE only; a cell without records
+        decodes to QueryMin, as the one-shot SQL ``min`` / ``max`` decode it.
+        Raises "round k, cell g: ... an answer changed between rounds" when a
+        ``min`` cell's answers contradict an earlier round; ``on_round`` gets the
+        list of the cells' digits."""
         op = sq.Query.Operation
         is_max = op.NameOp == "max"
 
@@ -206,19 +245,46 @@ class DrynxClient:
                     out.append(next((i for i, b in enumerate(nz) if (b == 0) == is_max), None))
             return out
 
-        def rule(k, prefix, ds):
+        def rule(k, prefixes, ds):
             digit, failed = ds[0], None
             if any(d != digit for d in ds):
                 failed = f"round {k}: the groups disagree on the digit ({ds})"
             elif digit is None and is_max:
                 failed = f"round {k}: no zero aggregate (the last output of a max round is always zero)"
             elif digit is None and k > 0:
-                failed = f"round {k}: no DP matches the prefix {prefix}: an answer changed between rounds"
+                failed = f"round {k}: no DP matches the prefix {prefixes[0]}: an answer changed between rounds"
             # min, round 0, no digit: no DP has records -> QueryMin, as the one-shot decode returns
-            return digit or 0, failed, digit is None and failed is None
+            return [digit or 0], failed, digit is None and failed is None
 
-        prefix, empty, rounds, _ = self._iterative_walk(sq, base, op.NameOp, digits, rule, on_round)
-        return float(op.QueryMin + (0 if empty else prefix)), rounds
+        cells = self._iter_cells(sq)
+        vacant = set()  # min: the cells without a record in round 0
+
+        def cell_rule(k, prefixes, ds):
+            ds, failed = self._cell_outs(k, cells, ds)
+            if failed is not None:
+                return [0] * cells, failed, False
+            for g, d in enumerate(ds):
+                if is_max:
+                    if d is None:
+                        failed = f"round {k}, cell {g}: no zero aggregate (the last output of a max round is zero)"
+                elif k == 0:
+                    if d is None:  # no record in the cell -> QueryMin, as the one-shot decode returns
+                        vacant.add(g)
+                elif d is None and g not in vacant:
+                    failed = (f"round {k}, cell {g}: no DP matches the prefix {prefixes[g]}: an answer changed "
+                              "between rounds")
+                elif d is not None and g in vacant:
+                    failed = (f"round {k}, cell {g}: a record in a cell that had none in round 0: an answer changed "
+                              "between rounds")
+                if failed is not None:
+                    break
+            return [d or 0 for d in ds], failed, False
+
+        prefixes, empty, rounds, _ = self._iterative_walk(sq, base, op.NameOp, digits,
+                                                          rule if cells is None else cell_rule, on_round)
+        if cells is not None:
+            return [float(op.QueryMin + p) for p in prefixes], rounds
+        return float(op.QueryMin + (0 if empty else prefixes[0])), rounds
 
     # ------------------------------------------------------------------ iterative quantiles
     def send_iterative_quantile(self, sq: SurveyQuery, base: int, num: int, den: int, on_round=None):
@@ -235,7 +301,16 @@ class DrynxClient:
         quantile and every round's SurveyResult (``client_out`` = the counts
         per group).  ``on_round(k, digit, result)`` is called after each round.
         Raises when a round's total is not the count of the bin chosen in the
-        round before, the groups disagree, or no DP has a record in the domain."""
+        round before, the groups disagree, or no DP has a record in the domain.
+
+        A survey with SQL (``SELECT median(x) ... WHERE ... GROUP BY ...``): one
+        search per cell, all in the same L rounds; every cell has its own rank
+        from its own round-0 total and its own consistency check ("round k,
+        cell g: ... an answer changed between rounds").  Returns ``([value per
+        cell], rounds)``, a list of one with WHERE only.  A cell without records
+        in round 0 yields NaN (what the logistic-regression cohorts return for
+        an empty cell); it keeps prefix 0 and must total 0 in every later
+        round.  Empty cells do not raise; ``on_round`` gets the list of digits."""
         num, den = int(num), int(den)
         if den < 1 or not 0 <= num <= den:
             raise ValueError(f"no quantile {num}/{den}")
@@ -249,34 +324,61 @@ class DrynxClient:
             with timers.timed("Decode"):
                 return [[int(round(v)) for v in self.decode(cv.to(self.device), round_op)] for cv in partial.groups()]
 
+        def step(c, t):
+            """``(digit, the rank left inside it)``: the smallest digit whose cumulative count reaches t."""
+            below = 0
+            for digit, x in enumerate(c):
+                if below + x >= t:
+                    break
+                below += x
+            return digit, t - below
+
         t, chosen = 0, 0  # the rank still to walk, the count of the bin chosen in the round before
 
-        def rule(k, prefix, cs):
+        def rule(k, prefixes, cs):
             nonlocal t, chosen
             c = cs[0]
             total = sum(c)
             if any(x != c for x in cs):
-                return 0, f"round {k}: the groups disagree on the counts", False
+                return [0], f"round {k}: the groups disagree on the counts", False
             if k == 0 and total == 0:
-                return 0, None, True
+                return [0], None, True
             if k == 0:
                 t = max(1, (num * total + den - 1) // den)
             elif total != chosen:
-                return 0, (f"round {k}: {total} records under the prefix {prefix}, round {k - 1} counted "
-                           f"{chosen}: an answer changed between rounds"), False
-            below = 0
-            for digit, x in enumerate(c):  # the smallest digit whose cumulative count reaches t
-                if below + x >= t:
-                    break
-                below += x
-            t -= below
+                return [0], (f"round {k}: {total} records under the prefix {prefixes[0]}, round {k - 1} counted "
+                             f"{chosen}: an answer changed between rounds"), False
+            digit, t = step(c, t)
             chosen = c[digit]
-            return digit, None, False
+            return [digit], None, False
 
-        prefix, empty, rounds, iter_id = self._iterative_walk(sq, base, "quantile", counts, rule, on_round)
+        cells = self._iter_cells(sq)
+        ts, chosens = [0] * (cells or 0), [0] * (cells or 0)  # per cell; a cell empty in round 0 keeps (0, 0)
+
+        def cell_rule(k, prefixes, cs):
+            cs, failed = self._cell_outs(k, cells, cs)
+            if failed is not None:
+                return [0] * cells, failed, False
+            digits = [0] * cells
+            for g, c in enumerate(cs):
+                total = sum(c)
+                if k == 0:
+                    ts[g] = max(1, (num * total + den - 1) // den) if total else 0
+                elif total != chosens[g]:
+                    return digits, (f"round {k}, cell {g}: {total} records under the prefix {prefixes[g]}, round "
+                                    f"{k - 1} counted {chosens[g]}: an answer changed between rounds"), False
+                if ts[g]:
+                    digits[g], ts[g] = step(c, ts[g])
+                    chosens[g] = c[digits[g]]
+            return digits, None, False
+
+        prefixes, empty, rounds, iter_id = self._iterative_walk(sq, base, "quantile", counts,
+                                                                rule if cells is None else cell_rule, on_round)
+        if cells is not None:
+            return [float(op.QueryMin + p) if ts[g] else float("nan") for g, p in enumerate(prefixes)], rounds
         if empty:
             raise RuntimeError(f"iterative quantile {iter_id}: no records in the domain")
-        return float(op.QueryMin + prefix), rounds
+        return float(op.QueryMin + prefixes[0]), rounds
 
     # ------------------------------------------------------------------ VN / skipchain calls
     def send_survey_query_to_vns(self, sq: SurveyQuery):

@@ -86,14 +86,15 @@ def make_survey(client: DrynxClient, cluster, op_name: str, *, query_min=0, quer
 def make_iterative_survey(client: DrynxClient, cluster, op_name: str, base: int, *, query_min=0, query_max=10,
                           rows=10, group_by=(1,), proofs=0, thresholds=None, survey_id=None, sig_device="cpu",
                           deterministic_sigs=False, verification_sharding=0, with_vns=None, range_proof_mode=0,
-                          ranges=None):
+                          ranges=None, sql=None):
     """The survey ``DrynxClient.send_iterative_extreme(sq, base)`` runs in rounds:
     a ``min``/``max`` over the full domain [query_min, query_max] whose ranges
     and input-validation signatures cover the ``base`` outputs of a round
     ((2, 1) each, made once and shared by every round) instead of one per
     value of the domain.  For ``frequencyCount`` it is the survey
     ``send_iterative_quantile`` runs: the outputs are counts, and with proofs
-    the ``ranges`` given ((u, l), or one per output) serve all ``base`` columns."""
+    the ``ranges`` given ((u, l), or one per output) serve all ``base`` columns.
+    ``sql``: ``make_survey``'s -- the searches then run per cell of the WHERE / GROUP BY."""
     from ..query import iter_operation
 
     if op_name == "frequencyCount":
@@ -105,7 +106,8 @@ def make_iterative_survey(client: DrynxClient, cluster, op_name: str, base: int,
     sq = make_survey(client, cluster, op_name, query_min=query_min, query_max=query_min + base - 1, rows=rows,
                      group_by=group_by, proofs=proofs, ranges=ranges, thresholds=thresholds,
                      survey_id=survey_id, sig_device=sig_device, deterministic_sigs=deterministic_sigs,
-                     verification_sharding=verification_sharding, with_vns=with_vns, range_proof_mode=range_proof_mode)
+                     verification_sharding=verification_sharding, with_vns=with_vns, range_proof_mode=range_proof_mode,
+                     sql=sql)
     sq.Query.Operation = iter_operation(op_name, query_min, query_max, base)
     sq.Query.DPDataGen.GenerateDataMax = int(query_max)
     sq.IterBase = int(base)

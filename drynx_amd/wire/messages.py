@@ -84,7 +84,8 @@ def survey_query_to_msg(sq: SurveyQuery) -> dict:
             "RosterVNs": roster_to_msg(q.RosterVNs) if q.RosterVNs is not None else None,
             # (every field empty encodes to the empty message a query without SQL sends)
             "SQL": {"Select": list(q.SQL.Select), "Where": [{"Name": w.Name, "Value": w.Value} for w in q.SQL.Where],
-                    "Predicate": q.SQL.Predicate, "GroupBy": list(q.SQL.GroupBy)},
+                    "Predicate": q.SQL.Predicate, "GroupBy": list(q.SQL.GroupBy),
+                    "IterPrefixes": [int(p) for p in sq.IterPrefixes]},  # (empty: not a byte)
             "CuttingFactor": q.CuttingFactor,
         },
         "IDtoPublic": {k: _pt(p) for k, p in sq.IDtoPublic.items()},
@@ -146,6 +147,7 @@ def survey_query_from_msg(d: dict) -> SurveyQuery:
         IterRound=int(d.get("IterRound") or 0),
         IterPrefix=int(d.get("IterPrefix") or 0),
         IterSurveyID=d.get("IterSurveyID") or "",
+        IterPrefixes=[int(p) for p in (q.get("SQL") or {}).get("IterPrefixes") or []],
     )
 
 

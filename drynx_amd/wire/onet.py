@@ -54,7 +54,12 @@ QUERY_IVSIGS = (("InputValidationSigs", ("rep", ("ptrslice", ("msg", PUBLISH_SIG
                 ("InputValidationSize1", "sint"), ("InputValidationSize2", "sint"))
 WHERE_CLEAR = (("Name", "string"), ("Value", "string"))
 QUERY_SQL = (("Select", ("rep", "string")), ("Where", ("rep", ("msg", WHERE_CLEAR))), ("Predicate", "string"),
-             ("GroupBy", ("rep", "string")))
+             ("GroupBy", ("rep", "string")),
+             # drynx_amd extension (after the reference fields): SurveyQuery.IterPrefixes, the prefix of every cell
+             # of the SQL plan in a round of an iterative query.  It travels here, with the cells it belongs to:
+             # the field list of SURVEY_QUERY_ITER is what every peer with the iterative extension sends and
+             # reads, and stays as it is.  An empty list is not encoded.
+             ("IterPrefixes", ("rep", "sint")))
 QUERY = (("Operation", ("msg", OPERATION)), ("Ranges", ("rep", ("ptrslice", "sint"))), ("Proofs", "sint"),
          ("Obfuscation", "bool"), ("DiffP", ("msg", QUERY_DIFFP)), ("DPDataGen", ("msg", QUERY_DPDATAGEN)),
          ("IVSigs", ("msg", QUERY_IVSIGS)), ("RosterVNs", ("msg", ROSTER)), ("SQL", ("msg", QUERY_SQL)),

@@ -27,6 +27,18 @@ events after a warm-up: the two-launch kernel pair (``native.iter_round``) for
 for ``frequencyCount`` on uniform records and with every record equal (all LDS
 atomics of a workgroup on one counter).
 
+``--groups V`` runs the searches over SQL cohorts: every DP holds a table (x,
+c1 uniform in [0, V), c2 uniform in [0, 3]), the survey carries ``GROUP BY c1``
+(and ``--where c2=1`` a WHERE term), and one walk finds the quantile or max of
+every cell (``SurveyQuery.IterPrefixes``).  A result is right when every cell's
+value equals the clear one of the redrawn tables (NaN, or the one-shot empty
+value QueryMin for ``max``, for a cell without records).  The one-shot SQL query
+alternates where V * N <= 100000.  The encoder alone is then the grouped digit
+histogram ``native.iter_round_cells`` for V in {1, 16, 256, 4096} at base 10 and
+1000, uniform keys against every row in one cell and one bin, beside
+``native.iter_round`` on the same records and ``native.group_moments(...,
+bins=...)`` on the last-round shape.
+
 ``--gpus W`` (W > 1) starts W ranks; the ranks without the querier serve the
 rounds (``serve_iterative``).  Prints one JSON object; ``--out-dir`` also
 writes it as range_<N>.json.
@@ -52,8 +64,8 @@ import bench  # noqa: E402  (the max configuration, the reference rows, the laun
 from drynx_amd import native as nt  # noqa: E402
 from drynx_amd.ops import encoding as enc  # noqa: E402
 from drynx_amd.parallel.comm import init_distributed, make_comm  # noqa: E402
-from drynx_amd.query import iter_rounds, new_survey_id  # noqa: E402
-from drynx_amd.rounds import max_base  # noqa: E402
+from drynx_amd.query import QuerySQL, WhereClear, iter_rounds, new_survey_id  # noqa: E402
+from drynx_amd.rounds import ITER_MAX_CELL_OUTPUTS, ITER_MAX_HIST_BASE, max_base  # noqa: E402
 from drynx_amd.services.api import DrynxClient, serve_iterative  # noqa: E402
 from drynx_amd.services.local import local_cluster, make_iterative_survey, make_survey  # noqa: E402
 from drynx_amd.utils import timers  # noqa: E402
@@ -76,6 +88,8 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--device", default=None)
     ap.add_argument("--no-classic", action="store_true", help="skip the one-shot query")
+    ap.add_argument("--groups", type=int, default=0, help="V > 0: GROUP BY c1 over V groups, one search per cell")
+    ap.add_argument("--where", default=None, help="with --groups: a WHERE term c2=<0..3> (e.g. c2=1)")
     ap.add_argument("--encoder-iters", type=int, default=200, help="encoder calls per timed window (GPU only)")
     ap.add_argument("--out-dir", default=None, help="write range_<N>.json here")
     ap.set_defaults(cns=3, dps=10, vns=3)
@@ -86,7 +100,15 @@ def parse():
         args.num, args.den = int(num), int(den or 1)
     except ValueError:
         ap.error("--bases is a comma-separated list of integers, --quantile is num/den")
-    top = max_base(OPERATION[args.query])
+    args.where_value = None
+    if args.where is not None:
+        col, _, val = args.where.partition("=")
+        if not args.groups or col != "c2" or not val.isdigit():
+            ap.error("--where c2=<value> goes with --groups")
+        args.where_value = int(val)
+    top = min(max_base(OPERATION[args.query]), ITER_MAX_HIST_BASE) if args.groups else max_base(OPERATION[args.query])
+    if args.groups < 0 or args.groups > 4096 or any(args.groups * b > ITER_MAX_CELL_OUTPUTS for b in args.base_list):
+        ap.error(f"--groups in 1..4096 with groups * base at most {ITER_MAX_CELL_OUTPUTS}")
     if args.passes < 1 or args.steps < 1 or args.rows < 1 or args.value_range < 2 or not args.base_list \
             or any(not 2 <= b <= top for b in args.base_list):
         ap.error(f"--passes, --steps and --rows at least 1, --range at least 2, bases in 2..{top}")
@@ -140,11 +162,18 @@ class MaxQuery:
         mx = comm.all_gather_object(max(mine, default=None))
         return max(v for v in mx if v is not None)
 
+    def clear_cell(self, values):
+        """A cell's clear result; without records what the one-shot SQL max decodes to (QueryMin = 0)."""
+        return max(values, default=0)
+
     def search(self, client, sq, base, on_round):
         return client.send_iterative_extreme(sq, base, on_round=on_round)
 
     def classic_value(self, vals):
         return vals[0][0]
+
+    def classic_cell(self, v):
+        return self.classic_value([v])
 
     def head(self, N, want):
         return {"clear_max": want}
@@ -178,11 +207,19 @@ class QuantileQuery:
     def clear(self, comm, mine):
         return nearest_rank([x for part in comm.all_gather_object(mine) for x in part], self.num, self.den)
 
+    def clear_cell(self, values):
+        """A cell's clear result, None (a NaN from the search) without records."""
+        return nearest_rank(values, self.num, self.den) if values else None
+
     def search(self, client, sq, base, on_round):
         return client.send_iterative_quantile(sq, base, self.num, self.den, on_round=on_round)
 
     def classic_value(self, vals):
         return quantile_of_histogram([int(round(v)) for v in vals[0]], self.num, self.den)
+
+    def classic_cell(self, v):
+        """A cell of the one-shot SQL query; NaN without records, as the search returns."""
+        return self.classic_value([v]) if any(int(round(x)) for x in v) else float("nan")
 
     def head(self, N, want):
         return {"quantile": f"{self.num}/{self.den}", "clear_quantile": want}
@@ -204,14 +241,44 @@ class QuantileQuery:
 
 QUERIES = {"max": MaxQuery, "quantile": QuantileQuery}
 
+COHORT_PROBE_WHAT = ("iter_round_cells('frequencyCount') (one launch per group window + the plan and prefix uploads), "
+                     "round 0 over base^2 values, GROUP BY over V groups: uniform keys vs every row in one cell and "
+                     "one bin; at V = 1 iter_round('frequencyCount') on the same records; group_moments(bins=) on "
+                     "the last-round shape (V x base cells); device events, three windows each, alternating")
+
+
+def cohort_probe_cases(rows, g, device):
+    n = sum(rows)
+    for b in (10, 1000):
+        R = b ** 2
+        x = torch.randint(0, R, (n,), generator=g, device=device)
+        for V in (1, 16, 256, 4096):
+            if V * b > ITER_MAX_CELL_OUTPUTS:
+                continue  # refused by the query rules and the entry alike
+            Ku = torch.stack([x, torch.randint(0, V, (n,), generator=g, device=device)], dim=1)
+            Ke = torch.stack([torch.full_like(x, R // 2), torch.full_like(x, V // 2)], dim=1)
+            keys, zero = [(1, 0, V)], [0] * V
+
+            def cells(K, keys=keys, zero=zero, b=b, R=R):
+                return lambda: nt.iter_round_cells("frequencyCount", K, rows, 0, 0, R - 1, b, 0, zero, keys)
+
+            calls = {"uniform": cells(Ku), "one_cell_one_bin": cells(Ke),
+                     "group_moments_bins": lambda K=Ku, keys=keys, b=b: nt.group_moments(
+                         K[:, :0], K, rows, [(0, 0)], keys, bins=(0, 0, b))}
+            if V == 1:
+                calls["iter_round"] = lambda K=Ku, b=b, R=R: nt.iter_round("frequencyCount", K, rows, 0, R - 1, b, 0, 0)
+                calls["iter_round_one_bin"] = lambda K=Ke, b=b, R=R: nt.iter_round("frequencyCount", K, rows, 0, R - 1,
+                                                                                  b, 0, 0)
+            yield f"base={b},V={V}", calls
+
 
 def encoder_alone(args, query, device) -> dict:
-    """ms per call of the query's kernel-probe cases (device events)."""
+    """ms per call of the query's kernel-probe cases (device events); with ``--groups`` the cohort cases."""
     g = torch.Generator(device=device).manual_seed(7)
     rows = [100_000] * 10
-    out = {"records": "10 DPs x 100000", "calls_per_window": args.encoder_iters, "what": query.probe_what,
-           "ms_per_call": {}}
-    for label, calls in query.probe_cases(rows, g, device):
+    out = {"records": "10 DPs x 100000", "calls_per_window": args.encoder_iters,
+           "what": COHORT_PROBE_WHAT if args.groups else query.probe_what, "ms_per_call": {}}
+    for label, calls in (cohort_probe_cases if args.groups else query.probe_cases)(rows, g, device):
         ms = {k: [] for k in calls}
         for f in calls.values():
             for _ in range(5):
@@ -250,9 +317,29 @@ def main():
     g = torch.Generator(device=device).manual_seed(99 + rank)  # bench.py's records
     node.dp_data = {dp.id: list(torch.randint(0, N, (1, rows), generator=g, device=device))
                     for dp in cl.local(rank, "dp")}
-    want = query.clear(comm, [int(x) for cols in node.dp_data.values() for x in cols[0].cpu().tolist()])
+    V, sql_kw = args.groups, {}
+    if V:  # the DPs' tables (x, c1, c2); one search per cell of GROUP BY c1 [WHERE c2 = value]
+        for cols in node.dp_data.values():
+            cols += [torch.randint(0, V, (rows,), generator=g, device=device),
+                     torch.randint(0, 4, (rows,), generator=g, device=device)]
+        mine = [r for cols in node.dp_data.values() for r in torch.stack(cols, dim=1).cpu().tolist()]
+        table = [r for part in comm.all_gather_object(mine) for r in part]
+        keep = [r for r in table if args.where_value is None or r[2] == args.where_value]
+        want = [query.clear_cell([x for x, c1, _ in keep if c1 == c]) for c in range(V)]
+        where = [] if args.where_value is None else [WhereClear("c2", str(args.where_value))]
+        sql_kw = {"group_by": (V,), "sql": QuerySQL(Where=where, GroupBy=["c1"])}
+    else:
+        want = query.clear(comm, [int(x) for cols in node.dp_data.values() for x in cols[0].cpu().tolist()])
+
+    def right(v):
+        """Is the decoded result the clear one (per cell with --groups: None stands for the NaN of an empty cell)?"""
+        if not V:
+            return int(round(v)) == want
+        return len(v) == V and all((w is None and x != x) or (w is not None and x == x and int(round(x)) == w)
+                                   for x, w in zip(v, want))
+
     client = DrynxClient(node, device=device) if rank == 0 else None
-    classic = not args.no_classic and N <= CLASSIC_MAX_RANGE
+    classic = not args.no_classic and max(1, V) * N <= CLASSIC_MAX_RANGE
     names = [f"base={b}" for b in args.base_list] + (["classic"] if classic else [])
     thresholds = [1.0, 1.0, 1.0, 0.0, 1.0]
     templates, sig_s = {}, {}
@@ -261,12 +348,13 @@ def main():
             t0 = time.perf_counter()
             if name == "classic":
                 templates[name] = make_survey(client, cl, op_name, query_min=0, query_max=N - 1, rows=rows, proofs=1,
-                                              ranges=query.classic_ranges, thresholds=thresholds, sig_device=device)
+                                              ranges=query.classic_ranges, thresholds=thresholds, sig_device=device,
+                                              **sql_kw)
             else:
                 kw = {} if query.ranges is None else {"ranges": query.ranges}
                 templates[name] = make_iterative_survey(client, cl, op_name, int(name[5:]), query_min=0,
                                                         query_max=N - 1, rows=rows, proofs=1, thresholds=thresholds,
-                                                        sig_device=device, **kw)
+                                                        sig_device=device, **kw, **sql_kw)
             sig_s[name] = round(time.perf_counter() - t0, 3)
 
     def one_step(name):
@@ -278,6 +366,8 @@ def main():
             sq = copy.copy(templates[name])
             sq.SurveyID = new_survey_id()
             _, vals, res = client.send_survey_query(sq)
+            if V:
+                return [query.classic_cell(v) for v in vals], [res.block], []
             return query.classic_value(vals), [res.block], []
         if rank != 0:
             serve_iterative(node)
@@ -325,13 +415,14 @@ def main():
                      "blocks_per_result": len(steps[0][1]),
                      "ms_per_round": round(sum(per_round) / len(per_round), 2) if per_round else None,
                      "round_ms": [rms for _, _, rms in steps],
-                     "all_proofs_valid": ok, "result_ok": all(int(round(v)) == want for v, _, _ in steps)})
+                     "all_proofs_valid": ok, "result_ok": all(right(v) for v, _, _ in steps)})
     encoder = encoder_alone(args, query, device) if rank == 0 and device.type == "cuda" and world == 1 else None
     node.close(remove=True)
     if rank != 0:
         return
     out = {"tool": "bench_iter", "query": args.query, "range": N, "steps_per_run": args.steps, "n_gpus": world,
            "device": device.type, "order": [r["query"] for r in runs], **query.head(N, want),
+           **({"groups": V, "where": args.where} if V else {}),
            "config": {"cns": args.cns, "vns": args.vns, "dps": n_dps, "records_per_dp": rows,
                       "range_proof": query.range_proof, "sigs": "random (per CN, per column)",
                       "thresholds": [1, 1, 1, 0, 1]},
@@ -360,7 +451,7 @@ def main():
     print(json.dumps(out), flush=True)
     if args.out_dir:
         os.makedirs(args.out_dir, exist_ok=True)
-        with open(os.path.join(args.out_dir, f"range_{N}.json"), "w") as f:
+        with open(os.path.join(args.out_dir, f"range_{N}_groups_{V}.json" if V else f"range_{N}.json"), "w") as f:
             json.dump(out, f, indent=1)
     if not (out["all_proofs_valid"] and out["result_ok"]):
         sys.exit("bench_iter: a proof was rejected or a decoded result is wrong")
