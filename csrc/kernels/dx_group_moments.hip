@@ -8,7 +8,9 @@
 // K14's).  A second matrix K [rows][CK] (its own row stride) holds the columns
 // the query filters and groups by:
 //
-//   where(i) : K[i][fcol_f] == fval_f for every filter term f (at most 8), and
+//   where(i) : K[i][fcol_f] == fval_f for every filter term f (at most 8) or,
+//              with a predicate, a formula of !, && and || over the atoms
+//              K[i][fcol_f] OP_f fval_f (== != < <= > >=, signed), and
 //   key(i)   : the mixed-radix number of the digits K[i][kcol_j] - koff_j over
 //              the cardinalities kcard_j, first column most significant (at
 //              most 4 columns and the counted one below); a row with a digit
@@ -79,6 +81,7 @@ inline size_t lds_bytes(int C, int cells) {
   return (size_t)cells * 8 + (size_t)kRows * stage_stride(C) * 8 + (size_t)kRows * 4;
 }
 
+template <bool General>  // a.general: the WHERE is a predicate
 __global__ void __launch_bounds__(kThreads) group_moments_kernel(GroupArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   const int cells = a.gw * a.P;
@@ -113,7 +116,7 @@ __global__ void __launch_bounds__(kThreads) group_moments_kernel(GroupArgs a) {
     }
     if (threadIdx.x < kRows) {
       const int r = threadIdx.x;
-      grp[r] = r < nr ? row_group(a, a.K + (base + r) * a.ldk) : -1;
+      grp[r] = r < nr ? row_group<General>(a, a.K + (base + r) * a.ldk) : -1;
     }
     __syncthreads();
 #pragma unroll
@@ -166,45 +169,61 @@ void host_group_moments(const GroupArgs &a, int64_t n_tiles) {
 
 extern "C" int dx_group_moments_max_cells() { return kMaxCells; }
 
-// keys [n_keys][3] = (column of K, offset, cardinality) and filters
-// [n_filters][2] = (column of K, value) are HOST arrays; K has CK columns.  out
+// keys [n_keys][3] = (column of K, offset, cardinality), filters
+// [n_filters][2] = (column of K, value) and pred (NULL: the conjunction of the
+// equalities; else n_filters operator codes and the four words of the truth
+// table, group_terms.h) are HOST arrays; K has CK columns.  out
 // [n_dp][G][P] with G the product of the cardinalities (1 without keys) is
 // zeroed by the caller before the first window; this call adds the groups
 // [g0, g0 + gw).  Every count, cardinality, column index and the cell cap is
 // checked here: an argument that does not fit returns -2 and launches nothing.
 namespace {
 // cell[i] = the group of row i among all G, G for a row that is dropped
+template <bool General>
 struct RowCells {
-  GroupArgs a;  // g0 = 0, gw = G: the window is every group
+  GroupArgs a;  // g0 = 0, gw = G: the window is every group; a.general == General
   int64_t *cell;
   __host__ __device__ void operator()(int64_t i) const {
-    const int g = row_group(a, a.K + i * a.ldk);
+    const int g = row_group<General>(a, a.K + i * a.ldk);
     cell[i] = g < 0 ? a.G : (int64_t)g;
   }
 };
+
+template <bool General>
+int run_cells(int on_gpu, void *stream, const GroupArgs &a, int64_t rows, int64_t *cell) {
+  return dx::run(on_gpu, stream, rows, RowCells<General>{a, cell}, false, "group_cells");
+}
 }  // namespace
 
 // The cell plan of a grouped encoder over other records than K14's (the
 // logistic-regression cohorts): cell[i] = the group of row i of K [rows][CK] by
 // the membership rule above (row_group, the very function of the moments), G =
-// the product of the cardinalities for a row that a filter term or an
-// out-of-range key digit drops.  keys and filters as below.
+// the product of the cardinalities for a row that the WHERE or an out-of-range
+// key digit drops.  keys, filters and pred as below.
+extern "C" int dx_group_cells_pred(int on_gpu, void *stream, const int64_t *K, int64_t ldk, int CK, int64_t rows,
+                                   const int64_t *keys, int n_keys, const int64_t *filters, int n_filters,
+                                   int64_t *cell, const int64_t *pred) {
+  GroupArgs a{};
+  if (rows < 0 || !set_terms(a, CK, keys, n_keys, filters, n_filters, pred)) return -2;
+  a.K = K, a.ldk = ldk, a.g0 = 0, a.gw = (int)a.G;
+  return a.general ? run_cells<true>(on_gpu, stream, a, rows, cell) : run_cells<false>(on_gpu, stream, a, rows, cell);
+}
+
+// pred == NULL under the signature the entry had before predicates
 extern "C" int dx_group_cells(int on_gpu, void *stream, const int64_t *K, int64_t ldk, int CK, int64_t rows,
                               const int64_t *keys, int n_keys, const int64_t *filters, int n_filters,
                               int64_t *cell) {
-  RowCells op{};
-  if (rows < 0 || !set_terms(op.a, CK, keys, n_keys, filters, n_filters)) return -2;
-  op.a.K = K, op.a.ldk = ldk, op.a.g0 = 0, op.a.gw = (int)op.a.G, op.cell = cell;
-  return dx::run(on_gpu, stream, rows, op, false, "group_cells");
+  return dx_group_cells_pred(on_gpu, stream, K, ldk, CK, rows, keys, n_keys, filters, n_filters, cell, nullptr);
 }
 
-extern "C" int dx_group_moments(int on_gpu, void *stream, const int64_t *Z, int64_t ldz, int C, const int64_t *K,
-                                int64_t ldk, int CK, const int64_t *tiles, int64_t n_tiles, const int16_t *pairs,
-                                int P, const int64_t *keys, int n_keys, const int64_t *filters, int n_filters,
-                                int64_t g0, int64_t gw, int64_t *out) {
+extern "C" int dx_group_moments_pred(int on_gpu, void *stream, const int64_t *Z, int64_t ldz, int C,
+                                     const int64_t *K, int64_t ldk, int CK, const int64_t *tiles, int64_t n_tiles,
+                                     const int16_t *pairs, int P, const int64_t *keys, int n_keys,
+                                     const int64_t *filters, int n_filters, int64_t g0, int64_t gw, int64_t *out,
+                                     const int64_t *pred) {
   if (C < 0 || C > kMaxCols || P <= 0 || P > kMaxPairs || n_tiles < 0 || n_tiles > 0x7fffffff) return -2;
   GroupArgs a{};
-  if (!set_terms(a, CK, keys, n_keys, filters, n_filters)) return -2;
+  if (!set_terms(a, CK, keys, n_keys, filters, n_filters, pred)) return -2;
   const int64_t G = a.G;
   if (g0 < 0 || gw < 1 || g0 + gw > G || gw * P > kMaxCells) return -2;
   if (n_tiles == 0) return 0;
@@ -217,11 +236,21 @@ extern "C" int dx_group_moments(int on_gpu, void *stream, const int64_t *Z, int6
   a.L = 1;
   while (a.L < kRows && P * a.L * 2 <= kThreads) a.L *= 2;
   const size_t bytes = lds_bytes(C, (int)(gw * P));
+  void (*const kernel)(GroupArgs) = a.general ? group_moments_kernel<true> : group_moments_kernel<false>;
   if (bytes > 48 * 1024)
-    if (int rc = dx::check_hip(hipFuncSetAttribute(reinterpret_cast<const void *>(group_moments_kernel),
+    if (int rc = dx::check_hip(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel),
                                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes),
                                "group_moments (LDS size)"))
       return rc;
-  hipLaunchKernelGGL(group_moments_kernel, dim3((unsigned)n_tiles), dim3(kThreads), bytes, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(kernel, dim3((unsigned)n_tiles), dim3(kThreads), bytes, (hipStream_t)stream, a);
   return dx::check_hip(hipGetLastError(), "group_moments");
+}
+
+// pred == NULL under the signature the entry had before predicates
+extern "C" int dx_group_moments(int on_gpu, void *stream, const int64_t *Z, int64_t ldz, int C, const int64_t *K,
+                                int64_t ldk, int CK, const int64_t *tiles, int64_t n_tiles, const int16_t *pairs,
+                                int P, const int64_t *keys, int n_keys, const int64_t *filters, int n_filters,
+                                int64_t g0, int64_t gw, int64_t *out) {
+  return dx_group_moments_pred(on_gpu, stream, Z, ldz, C, K, ldk, CK, tiles, n_tiles, pairs, P, keys, n_keys, filters,
+                               n_filters, g0, gw, out, nullptr);
 }

@@ -51,7 +51,8 @@
 //     out[dp][g][d] = #{ rows i of DP dp : row_group(i) == g, qmin <= x_i <= qmax,
 //                        (x_i - qmin) div hi == prefix[g], d == ((x_i - qmin) div lo) mod b }
 //
-// row_group is K14d's membership rule, the very function (group_terms.h); x_i
+// row_group is K14d's membership rule, the very function (group_terms.h: the
+// conjunction of equalities or a predicate over compared atoms, then the key); x_i
 // is column xcol of the key matrix K [rows][CK], read in place through its row
 // stride.  GPU: one 256-thread workgroup per tile of the host-made plan, the
 // tile's rows streamed with coalesced 64-bit loads, a row's group computed
@@ -323,9 +324,8 @@ struct CellArgs : dx::GroupTerms {  // G groups: out is [n_dp][G][base], zeroed 
 };
 
 // The counter (window-relative group * base + digit) of the row whose columns
-// are krow, -1 if the row does not count.
-__host__ __device__ inline int cell_counter(const CellArgs &a, const int64_t *krow) {
-  const int g = dx::row_group(a, krow);
+// are krow and whose group (row_group) is g, -1 if the row does not count.
+__host__ __device__ inline int cell_counter(const CellArgs &a, const int64_t *krow, int g) {
   if (g < 0) return -1;
   const int64_t x = krow[a.xcol];
   if (x < a.qmin || x > a.qmax) return -1;
@@ -335,6 +335,7 @@ __host__ __device__ inline int cell_counter(const CellArgs &a, const int64_t *kr
   return g * (int)a.base + (int)(q - p * (uint64_t)a.base);
 }
 
+template <bool General>  // a.general: the WHERE is a predicate (group_terms.h)
 __global__ void __launch_bounds__(kThreads) cell_hist_kernel(CellArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned int cell_cnt[];  // [gw][base]
   const int n = a.gw * (int)a.base;
@@ -343,7 +344,8 @@ __global__ void __launch_bounds__(kThreads) cell_hist_kernel(CellArgs a) {
   const int64_t dp = a.tiles[3 * (int64_t)blockIdx.x], r0 = a.tiles[3 * (int64_t)blockIdx.x + 1],
                 r1 = a.tiles[3 * (int64_t)blockIdx.x + 2];
   for (int64_t r = r0 + threadIdx.x; r < r1; r += kThreads) {
-    const int c = cell_counter(a, a.K + r * a.ldk);
+    const int64_t *krow = a.K + r * a.ldk;
+    const int c = cell_counter(a, krow, dx::row_group<General>(a, krow));
     if (c >= 0) atomicAdd(&cell_cnt[c], 1u);
   }
   __syncthreads();
@@ -357,30 +359,46 @@ void host_cell_hist(const CellArgs &a, int64_t n_tiles) {
     const int64_t dp = a.tiles[3 * t], r0 = a.tiles[3 * t + 1], r1 = a.tiles[3 * t + 2];
     uint64_t *o = reinterpret_cast<uint64_t *>(a.out) + (dp * a.G + a.g0) * a.base;
     for (int64_t r = r0; r < r1; r++) {
-      const int c = cell_counter(a, a.K + r * a.ldk);
+      const int64_t *krow = a.K + r * a.ldk;
+      const int c = cell_counter(a, krow, dx::row_group(a, krow));
       if (c >= 0) __atomic_fetch_add(o + c, (uint64_t)1, __ATOMIC_RELAXED);
     }
   });
+}
+
+// One window on the device.  The LDS limit of a kernel is raised once, to the
+// largest window, not per launch.
+template <bool General>
+int launch_cell_hist(const CellArgs &a, int64_t n_tiles, size_t bytes, void *stream) {
+  static const int lds_rc = dx::check_hip(
+      hipFuncSetAttribute(reinterpret_cast<const void *>(cell_hist_kernel<General>),
+                          hipFuncAttributeMaxDynamicSharedMemorySize, kMaxCounters * 4),
+      "iter_round_cells (LDS size)");
+  if (lds_rc) return lds_rc;
+  hipLaunchKernelGGL(cell_hist_kernel<General>, dim3((unsigned)n_tiles), dim3(kThreads), bytes, (hipStream_t)stream, a);
+  return dx::check_hip(hipGetLastError(), "iter_round_cells");
 }
 }  // namespace
 
 extern "C" int dx_iter_round_max_counters() { return kMaxCounters; }
 
-// One window of the grouped counts of a round.  keys [n_keys][3] and filters
-// [n_filters][2] are K14d's HOST arrays over K [rows][CK] (at most 4 keys: the
-// counted column xcol is not one of them), prefix [G] lives with K.  out
+// One window of the grouped counts of a round.  keys [n_keys][3], filters
+// [n_filters][2] and pred (NULL or the operators and the truth table) are
+// K14d's HOST arrays over K [rows][CK] (at most 4 keys: the counted column
+// xcol is not one of them), prefix [G] lives with K.  out
 // [n_dp][G][base] is zeroed by the caller before the first window; this call
 // adds the groups [g0, g0 + gw).  lo is b^(L-1-k) of round k, as dx_iter_round
 // takes it.  Everything that can be checked without reading device memory is
 // checked here -- the terms (the shared checker), xcol, the round, G * base, the
 // window, the counts, and on a host plan the tile length the 32-bit counters
 // allow: an argument that does not fit returns -2 and launches nothing.
-extern "C" int dx_iter_round_cells(int on_gpu, void *stream, const int64_t *K, int64_t ldk, int CK, int64_t xcol,
-                                   const int64_t *tiles, int64_t n_tiles, const int64_t *keys, int n_keys,
-                                   const int64_t *filters, int n_filters, int64_t qmin, int64_t qmax, int64_t base,
-                                   int64_t lo, const int64_t *prefix, int64_t g0, int64_t gw, int64_t *out) {
+extern "C" int dx_iter_round_cells_pred(int on_gpu, void *stream, const int64_t *K, int64_t ldk, int CK,
+                                        int64_t xcol, const int64_t *tiles, int64_t n_tiles, const int64_t *keys,
+                                        int n_keys, const int64_t *filters, int n_filters, int64_t qmin, int64_t qmax,
+                                        int64_t base, int64_t lo, const int64_t *prefix, int64_t g0, int64_t gw,
+                                        int64_t *out, const int64_t *pred) {
   CellArgs a{};
-  if (n_keys >= dx::kMaxKeys || !dx::set_terms(a, CK, keys, n_keys, filters, n_filters)) return -2;
+  if (n_keys >= dx::kMaxKeys || !dx::set_terms(a, CK, keys, n_keys, filters, n_filters, pred)) return -2;
   if (xcol < 0 || xcol >= CK) return -2;
   if (!is_round(kKindCounts, n_tiles, 0, qmin, qmax, base, lo, 0)) return -2;
   if (a.G * base > kMaxCellOutputs) return -2;
@@ -396,12 +414,15 @@ extern "C" int dx_iter_round_cells(int on_gpu, void *stream, const int64_t *K, i
     return 0;
   }
   const size_t bytes = (size_t)gw * (size_t)base * 4;
-  // the LDS limit of the kernel is raised once, to the largest window, not per launch
-  static const int lds_rc = dx::check_hip(
-      hipFuncSetAttribute(reinterpret_cast<const void *>(cell_hist_kernel),
-                          hipFuncAttributeMaxDynamicSharedMemorySize, kMaxCounters * 4),
-      "iter_round_cells (LDS size)");
-  if (lds_rc) return lds_rc;
-  hipLaunchKernelGGL(cell_hist_kernel, dim3((unsigned)n_tiles), dim3(kThreads), bytes, (hipStream_t)stream, a);
-  return dx::check_hip(hipGetLastError(), "iter_round_cells");
+  return a.general ? launch_cell_hist<true>(a, n_tiles, bytes, stream)
+                   : launch_cell_hist<false>(a, n_tiles, bytes, stream);
+}
+
+// pred == NULL under the signature the entry had before predicates
+extern "C" int dx_iter_round_cells(int on_gpu, void *stream, const int64_t *K, int64_t ldk, int CK, int64_t xcol,
+                                   const int64_t *tiles, int64_t n_tiles, const int64_t *keys, int n_keys,
+                                   const int64_t *filters, int n_filters, int64_t qmin, int64_t qmax, int64_t base,
+                                   int64_t lo, const int64_t *prefix, int64_t g0, int64_t gw, int64_t *out) {
+  return dx_iter_round_cells_pred(on_gpu, stream, K, ldk, CK, xcol, tiles, n_tiles, keys, n_keys, filters, n_filters,
+                                  qmin, qmax, base, lo, prefix, g0, gw, out, nullptr);
 }

@@ -49,18 +49,48 @@ def survey_set_operation(a):
     _write(cfg)
 
 
+_WHERE_OPS = (">=", "<=", "==", "!=", "<", ">", "=")  # two-character operators first
+
+
+def where_terms(terms, predicate: str):
+    """``--where COLUMN OP VALUE`` (repeatable) and ``--predicate`` -> ([(name,
+    value)], formula).  ``=`` and ``==`` are the equality of a plain
+    conjunction; any other operator makes the formula ``v0 OP v1 && v2 OP v3
+    ...`` here, which a ``--predicate`` of the caller's would contradict."""
+    where, ops = [], []
+    for term in terms or []:
+        at = [(term.find(op), op) for op in _WHERE_OPS if op in term]
+        if not at:
+            raise SystemExit(f"--where {term}: expected COLUMN=VALUE, or COLUMN OP VALUE with OP one of "
+                             "== != < <= > >=")
+        pos = min(p for p, _ in at)
+        op = next(o for p, o in at if p == pos)  # the longest operator at the first position
+        where.append((term[:pos].strip(), term[pos + len(op):].strip()))
+        ops.append("==" if op == "=" else op)
+    if any(op != "==" for op in ops):
+        if predicate:
+            raise SystemExit("--where with an operator other than = together with --predicate: write the "
+                             "comparisons into the formula (v0 >= v1 ...) and give --where COLUMN=VALUE terms")
+        predicate = " && ".join(f"v{2 * i} {op} v{2 * i + 1}" for i, op in enumerate(ops))
+    return where, predicate or ""
+
+
 def survey_run(a):
     """roster[0] is the CN (and the VN roster), roster[1:] are DPs; no proofs;
     GroupBy {3,2,1}; 10 rows in [0, 256] (survey.go:93-132).  ``--group-by c1,c3
-    --cardinalities 3,2``, ``--where c2=1`` (repeatable) and ``--select c0`` fill
-    the query's SQL (``query.QuerySQL``); with a GROUP BY every group's key and
-    result are printed, one line each."""
+    --cardinalities 3,2``, ``--where c2=1`` or ``--where 'c2>=2'`` (repeatable: a
+    conjunction), ``--predicate 'v0 == v1 || v2 < v3'`` (a formula over the
+    --where terms, ``QuerySQL.Predicate``) and ``--select c0`` fill the query's
+    SQL (``query.QuerySQL``); with a GROUP BY every group's key and result are
+    printed, one line each."""
     from ..crypto import oracle as O
     from ..query import (QueryDPDataGen, QueryDiffP, QuerySQL, Roster, ServerIdentity, WhereClear, check_parameters,
                          choose_operation)
     from ..services.api import DrynxClient
     from ..services.server import RemoteNode
 
+    terms, predicate = where_terms(a.where, a.predicate)  # refused here: nothing has been sent yet
+    where = [WhereClear(name, value) for name, value in terms]
     cfg = _read()
     nodes = cfg["Network"]["Nodes"]
     if len(nodes) < 2:
@@ -78,13 +108,7 @@ def survey_run(a):
     sq = client.generate_survey_query(roster, None, s2dp, id_to_pub, cfg["Survey"].get("Name"), op, None, None, 0,
                                       False, [0.0] * 5, QueryDiffP(), QueryDPDataGen([3, 2, 1], 10, 0, 256))
     csv = lambda v: [x.strip() for x in (v or "").split(",") if x.strip()]  # noqa: E731
-    where = []
-    for term in a.where or []:
-        name, eq, value = term.partition("=")
-        if not eq:
-            raise SystemExit(f"--where {term}: expected COLUMN=VALUE")
-        where.append(WhereClear(name.strip(), value.strip()))
-    sq.Query.SQL = QuerySQL(Select=csv(a.select), Where=where, GroupBy=csv(a.group_by))
+    sq.Query.SQL = QuerySQL(Select=csv(a.select), Where=where, Predicate=predicate, GroupBy=csv(a.group_by))
     if sq.Query.SQL.GroupBy:
         try:
             sq.Query.DPDataGen.GroupByValues = [int(v) for v in csv(a.cardinalities)]
@@ -127,7 +151,12 @@ def main(argv=None):
     p = sv.add_parser("run")
     p.add_argument("--group-by", default="", help="columns to group by, e.g. c1,c3")
     p.add_argument("--cardinalities", default="", help="values per --group-by column, e.g. 3,2")
-    p.add_argument("--where", action="append", help="COLUMN=VALUE, e.g. c2=1 (repeatable: a conjunction)")
+    p.add_argument("--where", action="append",
+                   help="COLUMN OP VALUE with OP one of = == != < <= > >=, e.g. c2=1 or 'c2>=2' (repeatable: a "
+                        "conjunction, or the terms of --predicate)")
+    p.add_argument("--predicate", default="",
+                   help="a formula over the --where terms, v{2i} the column and v{2i+1} the value of term i, "
+                        "e.g. 'v0 == v1 || !(v2 == v3)'")
     p.add_argument("--select", default="", help="the operation's input columns, e.g. c0")
     p.set_defaults(fn=survey_run)
     a = ap.parse_args(argv)

@@ -252,14 +252,15 @@ def _gpu_coefficients_int(Xs: list, ys: list, params: LogisticRegressionParamete
     m, s = _standardisation(params, Xs[0])
     precision = params.PrecisionApproxCoefficients
     if plan is not None:
-        keys, filters = _cohort_terms(params, plan)
+        keys, filters, predicate = _cohort_terms(params, plan)
     if params.Packing == 1:
         # distinct layout: the upper launch plan, then one reduce + pack + round launch
         packed = nt.lr_encode_packed_many(Xs, ys, m, s, 0.0, -1.0, precision) if plan is None else \
-            nt.lr_encode_cells_packed_many(Xs, ys, Ks, m, s, -1.0, keys, filters, precision)
+            nt.lr_encode_cells_packed_many(Xs, ys, Ks, m, s, -1.0, keys, filters, precision,
+                                           predicate=predicate)
         return packed[..., :T * D] if params.K == 1 else packed
     tot = nt.lr_encode_many(Xs, ys, m, s, 0.0, -1.0) if plan is None else \
-        nt.lr_encode_cells_many(Xs, ys, Ks, m, s, -1.0, keys, filters)
+        nt.lr_encode_cells_many(Xs, ys, Ks, m, s, -1.0, keys, filters, predicate=predicate)
     lv = tot[..., D:D + T, :D].flatten(-2)  # target-major level 1
     if params.K == 2:
         lv = torch.cat([lv, tot[..., :D, :D].flatten(-2)], -1)
@@ -285,13 +286,23 @@ def encode_coefficients_int_many(Xs: list, ys: list, params: LogisticRegressionP
 def cell_ids(K: torch.Tensor, plan) -> tuple:
     """The cell of every record under a query's SQL plan, from the DP's key
     table K [N, >= plan.width] int64 -> ([N] int64, G): the ``row_group`` rule
-    of the grouped moments in torch.  A record failing a Where term or with a
-    GroupBy value outside [0, V_i) gets G (dropped); otherwise the mixed-radix
+    of the grouped moments in torch.  A record failing the WHERE (a Where
+    equality, or ``plan.predicate`` over the terms' atoms) or with a GroupBy
+    value outside [0, V_i) gets G (dropped); otherwise the mixed-radix
     number of its GroupBy values, first column most significant
     (``all_possible_groups`` order); without GroupBy the one cell 0."""
     keep = torch.ones(K.shape[0], dtype=torch.bool, device=K.device)
-    for col, val in plan.where:
-        keep &= K[:, col] == val
+    if plan.predicate is None:
+        for col, val in plan.where:
+            keep &= K[:, col] == val
+    else:
+        ops, table = plan.predicate
+        cmp = {"==": torch.eq, "!=": torch.ne, "<": torch.lt, "<=": torch.le, ">": torch.gt, ">=": torch.ge}
+        idx = torch.zeros(K.shape[0], dtype=torch.int64, device=K.device)
+        for i, ((col, val), op) in enumerate(zip(plan.where, ops)):
+            idx |= cmp[op](K[:, col], val).to(torch.int64) << i
+        bits = torch.tensor([table >> i & 1 for i in range(1 << len(ops))], dtype=torch.bool, device=K.device)
+        keep = bits[idx]
     key = torch.zeros(K.shape[0], dtype=torch.int64, device=K.device)
     G = 1
     for col, card in plan.group_by:
@@ -303,10 +314,10 @@ def cell_ids(K: torch.Tensor, plan) -> tuple:
 
 
 def _cohort_terms(params, plan):
-    """(keys, filters) of the native grouped ops for a SQL plan, after the cohort rules."""
+    """(keys, filters, predicate) of the native grouped ops for a SQL plan, after the cohort rules."""
     if params.K != 2 or not (params.Means and params.StandardDeviations):
         raise ValueError("logistic regression over SQL cohorts needs K = 2 and global Means and StandardDeviations")
-    return [(c, 0, v) for c, v in plan.group_by], list(plan.where)
+    return [(c, 0, v) for c, v in plan.group_by], list(plan.where), plan.predicate
 
 
 def _key_table(K, n: int, plan, device) -> torch.Tensor:
@@ -331,7 +342,7 @@ def encode_coefficients_int_cells_many(Xs: list, ys: list, Ks: list, params: Log
     (``native.lr_encode_cells_many`` / ``..._packed_many``), one batch for the
     DPs.  Host: ``cell_ids``, then ``approx_coefficients`` on each cell's
     records -- the model the kernels are tested against."""
-    keys, filters = _cohort_terms(params, plan)
+    _cohort_terms(params, plan)  # the cohort rules
     T = n_targets(params)
     d = params.NbrFeatures
     D = d + 1

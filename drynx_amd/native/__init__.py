@@ -143,10 +143,13 @@ _SIGS = {
     "dx_int_moments": [_I, _P, _P, _L, _I, _P, _L, _P, _I, _P, _P],
     "dx_iter_round": [_I, _P, _P, _L, _P, _L, _P, _L, _I, _L, _L, _L, _L, _L, _P, _P],
     "dx_iter_round_cells": [_I, _P, _P, _L, _I, _L, _P, _L, _P, _I, _P, _I, _L, _L, _L, _L, _P, _L, _L, _P],
+    "dx_iter_round_cells_pred": [_I, _P, _P, _L, _I, _L, _P, _L, _P, _I, _P, _I, _L, _L, _L, _L, _P, _L, _L, _P, _P],
     "dx_iter_round_max_counters": [],
     "dx_group_moments": [_I, _P, _P, _L, _I, _P, _L, _I, _P, _L, _P, _I, _P, _I, _P, _I, _L, _L, _P],
+    "dx_group_moments_pred": [_I, _P, _P, _L, _I, _P, _L, _I, _P, _L, _P, _I, _P, _I, _P, _I, _L, _L, _P, _P],
     "dx_group_moments_max_cells": [],
     "dx_group_cells": [_I, _P, _P, _L, _I, _L, _P, _I, _P, _I, _P],
+    "dx_group_cells_pred": [_I, _P, _P, _L, _I, _L, _P, _I, _P, _I, _P, _P],
     "dx_sha256_rows": [_I, _P, _P, _L, _L, _L, _L, _P],
     "dx_sha256_segments": [_I, _P, _P, _L, _L, _L, _P],
     "dx_g1_aff_to_uv": [_I, _P, _P, _L],
@@ -1176,20 +1179,42 @@ GROUP_MOMENTS_MAX_GROUPS = 1 << 24
 # CU's 160 KiB leaves beside the staging area (csrc/kernels/dx_group_moments.hip
 # kMaxCells, exported as dx_group_moments_max_cells)
 GROUP_MOMENTS_MAX_CELLS = 5888
+# the operators of a predicate's atoms, in the order of their codes (csrc/kernels/group_terms.h kOpEq ..)
+GROUP_OPS = ("==", "!=", "<", "<=", ">", ">=")
 
 
-def _group_terms(what: str, K, n_rows: int, of: str, keys, filters, bins=None):
+def _group_terms(what: str, K, n_rows: int, of: str, keys, filters, bins=None, predicate=None):
     """The checked key and filter terms of a grouped op over the key matrix K
-    -> (keys, filters, columns of K, G): at most 4 ``(column, offset,
+    -> (keys, filters, columns of K, G, pred): at most 4 ``(column, offset,
     cardinality)`` and 8 ``(column, value)``, every column inside K, K int64
     with unit column stride and ``n_rows`` rows (those of ``of``), G = the
-    product of the cardinalities at most 2^24."""
+    product of the cardinalities at most 2^24.  ``predicate``: None (the rows
+    that equal every filter's value) or ``(ops, table)``, one operator of
+    ``GROUP_OPS`` per filter -- term f is the atom ``K[i, column_f] ops[f]
+    value_f`` -- and the truth table of the formula over the atoms as an int,
+    bit ``sum(atom_f << f)`` set where a row passes; pred is then the entries'
+    host array, the operator codes and the table's four 64-bit words."""
     keys = [tuple(int(x) for x in k) for k in keys]
     filters = [tuple(int(x) for x in f) for f in filters]
     if len(keys) > GROUP_MOMENTS_MAX_KEYS or any(len(k) != 3 for k in keys):
         raise ValueError(f"{what}: {len(keys)} key columns (at most {GROUP_MOMENTS_MAX_KEYS} triples)")
     if len(filters) > GROUP_MOMENTS_MAX_FILTERS or any(len(f) != 2 for f in filters):
         raise ValueError(f"{what}: {len(filters)} filter terms (at most {GROUP_MOMENTS_MAX_FILTERS} pairs)")
+    pred = None
+    if predicate is not None:
+        ops, table = predicate
+        ops, table = list(ops), int(table)
+        if not filters:
+            raise ValueError(f"{what}: a predicate without filter terms")
+        if len(ops) != len(filters):
+            raise ValueError(f"{what}: {len(ops)} operators for {len(filters)} filter terms")
+        for op in ops:
+            if op not in GROUP_OPS:
+                raise ValueError(f"{what}: unknown operator {op!r} (one of {' '.join(GROUP_OPS)})")
+        if not 0 <= table < 1 << (1 << len(filters)):
+            raise ValueError(f"{what}: a truth table outside [0, 2^{1 << len(filters)}) for {len(filters)} atoms")
+        words = np.array([(table >> (64 * w)) & ((1 << 64) - 1) for w in range(4)], dtype=np.uint64)
+        pred = np.concatenate([np.array([GROUP_OPS.index(op) for op in ops], dtype=np.int64), words.view(np.int64)])
     if bins is not None:
         keys = keys + [tuple(int(x) for x in bins)]
         if len(keys[-1]) != 3:
@@ -1210,11 +1235,19 @@ def _group_terms(what: str, K, n_rows: int, of: str, keys, filters, bins=None):
     for col in [k[0] for k in keys] + [f[0] for f in filters]:
         if not 0 <= col < CK:
             raise ValueError(f"{what}: column {col} of a {CK}-column key matrix")
-    return keys, filters, CK, G
+    return keys, filters, CK, G, pred
+
+
+def _terms_call(name: str, pred, *args) -> int:
+    """A grouped entry's return code: ``name`` itself without a predicate, its
+    ``_pred`` form with the predicate's host array as one more, last argument."""
+    if pred is None:
+        return _raw_call(name, *args)
+    return _raw_call(name + "_pred", *args, pred.ctypes.data_as(_P))
 
 
 def group_moments(Z: torch.Tensor, K: torch.Tensor | None, seg_rows, pairs, keys=(), filters=(),
-                  bins=None) -> torch.Tensor:
+                  bins=None, predicate=None) -> torch.Tensor:
     """K14d (csrc/kernels/dx_group_moments.hip): ``int_moments`` filtered and
     grouped, ``out[dp, g, p] = sum over the rows i of segment dp with where(i)
     and key(i) == g of Z[i, a_p] * Z[i, b_p]`` (mod 2^64) -> [n_dp, G, P] int64.
@@ -1228,6 +1261,10 @@ def group_moments(Z: torch.Tensor, K: torch.Tensor | None, seg_rows, pairs, keys
     a digit outside ``[0, cardinality)`` is dropped; G is the product of the
     cardinalities (1 without keys).  ``filters``: up to 8 ``(column of K,
     value)``; a row counts if every one of its columns equals the value.
+    ``predicate``: ``(ops, table)``, which turns the filters into the atoms
+    ``column ops[f] value`` (``GROUP_OPS``, signed) of a formula given by its
+    truth table over the atom bits (``_group_terms``); a row counts if the
+    formula holds for it.
     ``bins``: one more, innermost key triple beside the 4 -- the counted column
     (x, QueryMin, R) of a frequency count, whose (group, bin) cells are groups.
 
@@ -1239,7 +1276,7 @@ def group_moments(Z: torch.Tensor, K: torch.Tensor | None, seg_rows, pairs, keys
     pr = np.asarray(pairs, dtype=np.int16).reshape(-1, 2)
     if C > INT_MOMENTS_MAX_COLS or pr.size == 0 or pr.min() < 0 or pr.max() > C:
         raise ValueError(f"group_moments: {C} columns, pairs out of range")
-    keys, filters, CK, G = _group_terms("group_moments", K, Z.shape[0], "Z", keys, filters, bins)
+    keys, filters, CK, G, pred = _group_terms("group_moments", K, Z.shape[0], "Z", keys, filters, bins, predicate)
     counts = np.asarray(seg_rows, dtype=np.int64).reshape(-1)
     n_dp, P = len(counts), pr.shape[0]
     if counts.sum() != Z.shape[0] or (n_dp and counts.min() < 0):
@@ -1258,10 +1295,10 @@ def group_moments(Z: torch.Tensor, K: torch.Tensor | None, seg_rows, pairs, keys
     fd = np.ascontiguousarray(np.asarray(filters, dtype=np.int64).reshape(-1))
     g, s = _ctx(Zc, K)
     for g0 in range(0, G, gw):
-        rc = _raw_call("dx_group_moments", g, s, _ptr(Zc), Zc.stride(0) if C else 0, C,
-                       _ptr(K, strided=True), K.stride(0) if CK else 0, CK, _ptr(tiles), n_tiles, _ptr(pairs_t), P,
-                       kd.ctypes.data_as(_P), len(keys), fd.ctypes.data_as(_P), len(filters), g0, min(gw, G - g0),
-                       _ptr(out))
+        rc = _terms_call("dx_group_moments", pred, g, s, _ptr(Zc), Zc.stride(0) if C else 0, C,
+                         _ptr(K, strided=True), K.stride(0) if CK else 0, CK, _ptr(tiles), n_tiles, _ptr(pairs_t), P,
+                         kd.ctypes.data_as(_P), len(keys), fd.ctypes.data_as(_P), len(filters), g0, min(gw, G - g0),
+                         _ptr(out))
         if rc == -2:
             raise ValueError("group_moments: the entry refused its arguments")
         if rc != 0:
@@ -1346,14 +1383,14 @@ ITER_ROUND_MAX_COUNTERS = 20480
 
 
 def iter_round_cells(name: str, K: torch.Tensor, seg_rows, xcol: int, qmin: int, qmax: int, base: int, round: int,
-                     prefixes, keys=(), filters=()) -> torch.Tensor:
+                     prefixes, keys=(), filters=(), predicate=None) -> torch.Tensor:
     """K14e (csrc/kernels/dx_iter_round.hip, dx_iter_round_cells): the [n_dp, G,
     base] int64 rows every DP of a batch encrypts in round ``round`` of G
     simultaneous iterative ``name`` searches, one per cell of a WHERE / GROUP BY.
 
     K [rows, CK] int64 holds the DPs' record tables back to back (``seg_rows[d]``
     rows for DP d) and is read in place through its row stride; ``keys`` and
-    ``filters`` are ``group_moments``' (at most 4 keys), G the product of the
+    ``filters`` and ``predicate`` are ``group_moments``' (at most 4 keys), G the product of the
     cardinalities, and column ``xcol`` of K is the counted one.  Cell g counts
     the rows of its group (``group_moments``' membership rule, the same
     function) with x inside [qmin, qmax] and (x - qmin) div base^(L-round) ==
@@ -1370,7 +1407,7 @@ def iter_round_cells(name: str, K: torch.Tensor, seg_rows, xcol: int, qmin: int,
     assert K.dtype == torch.int64 and K.dim() == 2
     qmin, qmax, base, xcol = int(qmin), int(qmax), int(base), int(xcol)
     what = f"iterative {name} over cells"
-    keys, filters, CK, G = _group_terms(what, K, K.shape[0], "K", keys, filters)
+    keys, filters, CK, G, pred = _group_terms(what, K, K.shape[0], "K", keys, filters, predicate=predicate)
     prefixes = [int(p) for p in prefixes]
     _, lo = rounds.iter_round_cells(name, qmin, qmax, base, round, prefixes, G)
     if not 0 <= xcol < CK:
@@ -1394,9 +1431,9 @@ def iter_round_cells(name: str, K: torch.Tensor, seg_rows, xcol: int, qmin: int,
     fd = np.ascontiguousarray(np.asarray(filters, dtype=np.int64).reshape(-1))
     g, s = _ctx(K)
     for g0 in range(0, G, gw):
-        rc = _raw_call("dx_iter_round_cells", g, s, _ptr(K, strided=True), K.stride(0), CK, xcol, _ptr(tiles),
-                       n_tiles, kd.ctypes.data_as(_P), len(keys), fd.ctypes.data_as(_P), len(filters), qmin, qmax,
-                       base, lo, _ptr(pre), g0, min(gw, G - g0), _ptr(out))
+        rc = _terms_call("dx_iter_round_cells", pred, g, s, _ptr(K, strided=True), K.stride(0), CK, xcol, _ptr(tiles),
+                         n_tiles, kd.ctypes.data_as(_P), len(keys), fd.ctypes.data_as(_P), len(filters), qmin, qmax,
+                         base, lo, _ptr(pre), g0, min(gw, G - g0), _ptr(out))
         if rc == -2:
             raise ValueError(f"{what}: the entry refused its arguments")
         if rc != 0:
@@ -1670,9 +1707,10 @@ def _lr_cell_blocks(N: int, G: int) -> int:
     return _lr_blocks(-(-int(N) // max(1, int(G))))
 
 
-def _group_cells(K: torch.Tensor | None, n_rows: int, keys, filters, device):
+def _group_cells(K: torch.Tensor | None, n_rows: int, keys, filters, device, predicate=None):
     """``group_cells`` -> (cells, G)."""
-    keys, filters, CK, G = _group_terms("group_cells", K, n_rows, "the records", keys, filters)
+    keys, filters, CK, G, pred = _group_terms("group_cells", K, n_rows, "the records", keys, filters,
+                                              predicate=predicate)
     if K is None:
         return torch.zeros(n_rows, dtype=torch.int64, device=device), G
     cell = torch.empty(n_rows, dtype=torch.int64, device=K.device)
@@ -1681,8 +1719,8 @@ def _group_cells(K: torch.Tensor | None, n_rows: int, keys, filters, device):
     kd = np.ascontiguousarray(np.asarray(keys, dtype=np.int64).reshape(-1))
     fd = np.ascontiguousarray(np.asarray(filters, dtype=np.int64).reshape(-1))
     g, s = _ctx(K)
-    rc = _raw_call("dx_group_cells", g, s, _ptr(K, strided=True), K.stride(0) if CK else 0, CK, n_rows,
-                   kd.ctypes.data_as(_P), len(keys), fd.ctypes.data_as(_P), len(filters), _ptr(cell))
+    rc = _terms_call("dx_group_cells", pred, g, s, _ptr(K, strided=True), K.stride(0) if CK else 0, CK, n_rows,
+                     kd.ctypes.data_as(_P), len(keys), fd.ctypes.data_as(_P), len(filters), _ptr(cell))
     if rc == -2:
         raise ValueError("group_cells: the entry refused its arguments")
     if rc != 0:
@@ -1690,29 +1728,31 @@ def _group_cells(K: torch.Tensor | None, n_rows: int, keys, filters, device):
     return cell, G
 
 
-def group_cells(K: torch.Tensor | None, n_rows: int, keys=(), filters=(), device=None) -> torch.Tensor:
+def group_cells(K: torch.Tensor | None, n_rows: int, keys=(), filters=(), device=None,
+                predicate=None) -> torch.Tensor:
     """The cell of every row of the key matrix K [rows, CK] -> [rows] int64
     (dx_group_cells, ``group_moments``' membership rule and argument checks):
     the mixed-radix group index over ``keys``, or G (the number of groups) for a
-    row that a filter term or an out-of-range key digit drops.  K is read in
-    place through its row stride; None without keys and filters (one cell)."""
-    return _group_cells(K, n_rows, keys, filters, device)[0]
+    row that a filter term (with ``predicate``: the formula over the filters'
+    atoms) or an out-of-range key digit drops.  K is read in place through its
+    row stride; None without keys and filters (one cell)."""
+    return _group_cells(K, n_rows, keys, filters, device, predicate)[0]
 
 
-def lr_cell_plan(K: torch.Tensor | None, n_rows: int, keys=(), filters=(), device=None):
+def lr_cell_plan(K: torch.Tensor | None, n_rows: int, keys=(), filters=(), device=None, predicate=None):
     """The cell plan of one DP's records -> (perm, cell_start, G): the rows that
     belong to a cell, grouped by cell with the record order kept inside a cell
     (a stable sort of ``group_cells``; dropped rows sort behind the last cell),
     and the cells' bounds in it, [G + 1].  Device ops only: nothing is copied
     to the host."""
-    cell, G = _group_cells(K, n_rows, keys, filters, device)
+    cell, G = _group_cells(K, n_rows, keys, filters, device, predicate)
     ids, perm = torch.sort(cell, stable=True)
     cell_start = torch.searchsorted(ids, torch.arange(G + 1, dtype=torch.int64, device=cell.device))
     return perm, cell_start, G
 
 
 def _lr_cells_run(Xs: list, ys: list, Ks: list, mean, sd, wb: float, keys, filters, upper: bool, max_slab_bytes,
-                  pack=None):
+                  pack=None, predicate=None):
     """The grouped encoder DP by DP and window by window -> (out, fout).  Every
     window's [cw, nbc, P, P] slab is reduced straight into ``out[dp, c0:c0 +
     cw]``: by ``lr_reduce`` into totals [n, G, P, P], or, with ``pack =
@@ -1731,7 +1771,7 @@ def _lr_cells_run(Xs: list, ys: list, Ks: list, mean, sd, wb: float, keys, filte
         N = X.shape[0]
         if K is not None and K.device != dev:
             raise ValueError(f"native op mixes devices {dev} and {K.device}")
-        perm, cell_start, G = lr_cell_plan(K, N, keys, filters, dev)
+        perm, cell_start, G = lr_cell_plan(K, N, keys, filters, dev, predicate)
         if out is None:  # G is the first plan's: the keys' cardinalities, the same for every DP
             if pack is None:
                 out = torch.empty((len(Xs), G, p.P, p.P), dtype=torch.float64, device=dev)
@@ -1758,32 +1798,34 @@ def _lr_cells_run(Xs: list, ys: list, Ks: list, mean, sd, wb: float, keys, filte
 
 
 def lr_encode_cells_many(Xs: list, ys: list, Ks: list, mean, sd, wb: float, keys=(), filters=(), *,
-                         upper: bool = False, max_slab_bytes: int = LR_CELLS_MAX_SLAB_BYTES) -> torch.Tensor:
+                         upper: bool = False, max_slab_bytes: int = LR_CELLS_MAX_SLAB_BYTES,
+                         predicate=None) -> torch.Tensor:
     """``lr_encode_many`` per cell of a WHERE / GROUP BY over the DPs' records
     (the fused fp64-MFMA encoder with the rows read through a cell plan) ->
     [n, G, P, P] totals: for cell c of DP i level 2 (weight
     ``wb``) in [:D, :D] and level 1 in rows D..D+T-1, summed over the records of
     the cell; an empty cell is zeros.  ``Ks[i]`` [N_i, CK] int64 holds the key
     and filter columns of DP i's records row for row (read in place through its
-    row stride; None without keys and filters); ``keys`` / ``filters`` and their
-    limits are ``group_moments``'.  Per DP the cells are encoded in windows whose
+    row stride; None without keys and filters); ``keys`` / ``filters`` /
+    ``predicate`` and their limits are ``group_moments``'.  Per DP the cells are encoded in windows whose
     partial slab stays within ``max_slab_bytes``; every window is finished by
     dx_lr_reduce with the cells as items, so a cell is the same bits whatever
     the windows and whichever DPs share the batch.  ``upper``: the packed
     layout's launch plan (what it skips is left zero or unwritten).  One cell
     and no filter: ``lr_encode_many``'s bits."""
-    return _lr_cells_run(Xs, ys, Ks, mean, sd, wb, keys, filters, upper, max_slab_bytes)[0]
+    return _lr_cells_run(Xs, ys, Ks, mean, sd, wb, keys, filters, upper, max_slab_bytes, predicate=predicate)[0]
 
 
 def lr_encode_cells_packed_many(Xs: list, ys: list, Ks: list, mean, sd, wb: float, keys=(), filters=(),
                                 precision: float = 1.0, *, floats: bool = False,
-                                max_slab_bytes: int = LR_CELLS_MAX_SLAB_BYTES):
+                                max_slab_bytes: int = LR_CELLS_MAX_SLAB_BYTES, predicate=None):
     """``lr_encode_packed_many`` per cell: the distinct-coefficient integer
     vectors -> int64 [n, G, T*D + D(D+1)/2] (``floats``: and the unrounded fp64
     values), the encoder's upper launch plan per window and ONE reduce + pack +
     round launch (dx_lr_reduce_pack) per window with the cells as items.  Entry
     (i, j), i <= j, of a cell is the same bits as ``lr_encode_cells_many``'s."""
-    out, fout = _lr_cells_run(Xs, ys, Ks, mean, sd, wb, keys, filters, True, max_slab_bytes, (precision, floats))
+    out, fout = _lr_cells_run(Xs, ys, Ks, mean, sd, wb, keys, filters, True, max_slab_bytes, (precision, floats),
+                              predicate)
     return (out, fout) if floats else out
 
 

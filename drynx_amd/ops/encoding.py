@@ -227,7 +227,8 @@ def batch_values_sql(name: str, Z: torch.Tensor, K: torch.Tensor, seg_rows, sql_
                      qmax: int = 0) -> torch.Tensor:
     """[n_dp, ng, n_out] int64 outputs of every (DP, group) cell of a batch for
     a query with ``Query.SQL``, on Z's device: ``batch_values`` over the records
-    that pass the WHERE conjunction, per GROUP BY group (ng = 1 without one).
+    that pass the WHERE (the conjunction of equalities, or ``sql_plan.predicate``
+    over the terms), per GROUP BY group (ng = 1 without one).
 
     Z [rows, n_in] holds the operation's input columns (the SQL ``Select``) as
     ``batch_values`` takes them, K [rows, width] the DPs' record tables, which
@@ -253,11 +254,13 @@ def batch_values_sql(name: str, Z: torch.Tensor, K: torch.Tensor, seg_rows, sql_
             Z = torch.stack([Z[:, 0], Z[:, 1] - Z[:, 0]], dim=1)
         elif name in ("sum", "mean", "variance"):
             Z = Z[:, :1]
-        return nt.group_moments(Z.contiguous(), K, seg_rows, moment_pairs(name, Z.shape[1]), keys, filters)
+        return nt.group_moments(Z.contiguous(), K, seg_rows, moment_pairs(name, Z.shape[1]), keys, filters,
+                                predicate=sql_plan.predicate)
     if name not in COUNT_OPS:
         raise ValueError(f"{name} has no SQL encoder")
     n = qmax - qmin + 1
-    cnt = nt.group_moments(Z[:, :0], K, seg_rows, [(0, 0)], keys, filters, bins=(sql_plan.select[0], qmin, n))
+    cnt = nt.group_moments(Z[:, :0], K, seg_rows, [(0, 0)], keys, filters, bins=(sql_plan.select[0], qmin, n),
+                           predicate=sql_plan.predicate)
     cnt = cnt.reshape(len(seg_rows), -1, n)
     return nt.rows_of_counts(name, cnt)
 
@@ -285,7 +288,7 @@ def iterative_values_sql(operation: Operation, K: torch.Tensor, seg_rows, plan, 
     ``Query.SQL``: G simultaneous searches, one per cell of ``plan``
     (``query.SQLPlan``) in ``all_possible_groups`` order, cell g under
     ``prefixes[g]``.  K [rows, width] stacks the DPs' record tables; a cell's
-    records are the rows that pass the WHERE conjunction and carry its key
+    records are the rows that pass the WHERE (``plan.predicate`` included) and carry its key
     digits (``batch_values_sql``'s rule), with the counted column
     ``plan.select[0]`` inside the domain and under the cell's prefix.
     frequencyCount: the digit's counts; min / max: [an occupied digit at or
@@ -303,7 +306,7 @@ def iterative_values_sql(operation: Operation, K: torch.Tensor, seg_rows, plan, 
         raise ValueError(f"{operation.NameOp} has no iterative rounds")
     keys = [(c, 0, v) for c, v in plan.group_by]
     return nt.iter_round_cells(operation.NameOp, K, seg_rows, plan.select[0], operation.QueryMin, operation.QueryMax,
-                               base, rnd, prefixes, keys, list(plan.where))
+                               base, rnd, prefixes, keys, list(plan.where), plan.predicate)
 
 
 def encode_iterative(data, operation: Operation, base: int, rnd: int, prefix: int, pk, with_proofs=False,

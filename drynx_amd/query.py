@@ -156,8 +156,9 @@ class Operation:
 
 @dataclass
 class WhereClear:
-    """One equality of a WHERE clause (structs.go WhereQueryAttributeClear):
-    column ``Name`` == int(``Value``)."""
+    """One term of a WHERE clause (structs.go WhereQueryAttributeClear): column
+    ``Name`` == int(``Value``), or the atom ``Name`` OP int(``Value``) that
+    ``QuerySQL.Predicate`` makes of it."""
     Name: str = ""
     Value: str = ""
 
@@ -170,8 +171,18 @@ class QuerySQL:
     * a column name is ``c<k>``, the zero-based column k < 64 of a DP's record table;
     * ``Select``: the NbrInput columns the operation reads, in its input order
       (empty: c0 .. c{NbrInput-1});
-    * ``Where``: a conjunction of at most 8 equalities column == int(Value);
-      ``Predicate`` must stay empty (only the conjunction is defined);
+    * ``Where``: at most 8 terms (column, int(Value)).  With an empty
+      ``Predicate`` a record passes if every column equals its value (the
+      conjunction of equalities);
+    * ``Predicate``: a formula in the UnLynx syntax over the Where terms, where
+      ``v{2i}`` names the column of ``Where[i]`` and ``v{2i+1}`` its value.  An
+      atom is ``v{2i} OP v{2i+1}`` with OP one of ``== != < <= > >=`` (signed
+      int64, exact at both ends); atoms combine with ``!``, ``&&`` (binds
+      tighter), ``||`` and parentheses, ASCII spaces allowed, at most 256
+      characters and 16 nested parentheses.  Every Where term appears in exactly
+      one atom (a column compared twice is listed twice), and a record passes
+      if the formula holds for it: ``v0 >= v1 && v2 < v3`` with Where = [(c4,
+      40), (c4, 65)] is 40 <= c4 < 65;
     * ``GroupBy``: at most 4 columns; ``DPDataGen.GroupByValues[i]`` is the
       cardinality V_i of ``GroupBy[i]`` (product at most 4096), a record belongs
       to the group of its values in those columns, in ``all_possible_groups``
@@ -218,16 +229,144 @@ def sql_column(name) -> int:
     return k
 
 
+SQL_MAX_PREDICATE_CHARS = 256
+SQL_MAX_PREDICATE_DEPTH = 16
+SQL_COMPARISONS = ("==", "!=", "<", "<=", ">", ">=")  # native.GROUP_OPS
+_NO_PREDICATE = "without a predicate only the conjunction of the Where equalities is defined"
+
+
+def _predicate_tokens(text: str) -> list:
+    """The tokens of a predicate formula: ("v", k), a comparison, "!", "&&",
+    "||", "(" or ")".  ValueError (the complaint alone) for anything else."""
+    out, i = [], 0
+    while i < len(text):
+        c = text[i]
+        if c == " ":
+            i += 1
+        elif c == "v":
+            j = i + 1
+            while j < len(text) and text[j] in "0123456789":
+                j += 1
+            digits = text[i + 1:j]
+            if not digits or (len(digits) > 1 and digits[0] == "0") or len(digits) > 3:
+                raise ValueError(f"has the malformed variable {text[i:j]!r} (v<k>, no leading zeros)")
+            out.append(("v", int(digits)))
+            i = j
+        elif text[i:i + 2] in ("==", "!=", "<=", ">=", "&&", "||"):
+            out.append(text[i:i + 2])
+            i += 2
+        elif c in "<>!()":
+            out.append(c)
+            i += 1
+        else:
+            raise ValueError(f"has the unknown token {text[i:i + 2].strip()!r}")
+    return out
+
+
+def parse_predicate(text: str, n_terms: int) -> tuple:
+    """``QuerySQL.Predicate`` over ``n_terms`` Where terms -> (ops, table): the
+    operator of every term's atom ``v{2i} OP v{2i+1}`` and the formula's truth
+    table over the atom bits (atom i is bit i of the index) as an int below
+    2^(2^n_terms).  ``&&`` binds tighter than ``||``; ``!`` applies to an atom,
+    a parenthesis or another ``!``.  Raises ValueError with the complaint alone
+    (``sql_plan`` words the refusal).  The formula is not trusted: its length
+    and its nesting are capped before anything is built, and the parser keeps
+    its own stack."""
+    if n_terms < 1:
+        raise ValueError("set with no Where term to compare")
+    if len(text) > SQL_MAX_PREDICATE_CHARS:
+        raise ValueError(f"is longer than {SQL_MAX_PREDICATE_CHARS} characters")
+    if not text.isascii():
+        raise ValueError("has a character outside ASCII")
+    toks = _predicate_tokens(text)
+    full = (1 << (1 << n_terms)) - 1
+    ops = [None] * n_terms
+    # one frame per open parenthesis: [pending negations, the || operands so far, the && operands of the last one]
+    stack = [[0, [], []]]
+    i, want_operand = 0, True
+
+    def operand(t):
+        frame = stack[-1]
+        frame[2].append(full ^ t if frame[0] & 1 else t)
+        frame[0] = 0
+
+    def close(frame):
+        conj = full
+        for t in frame[2]:
+            conj &= t
+        return frame[1] + [conj]
+
+    while i < len(toks):
+        t = toks[i]
+        if want_operand:
+            if t == "!":
+                stack[-1][0] += 1
+                i += 1
+            elif t == "(":
+                if len(stack) > SQL_MAX_PREDICATE_DEPTH:
+                    raise ValueError(f"nests deeper than {SQL_MAX_PREDICATE_DEPTH} parentheses")
+                stack.append([0, [], []])
+                i += 1
+            elif isinstance(t, tuple):
+                a, op, b = t[1], toks[i + 1] if i + 1 < len(toks) else None, toks[i + 2] if i + 2 < len(toks) else None
+                if op not in SQL_COMPARISONS or not isinstance(b, tuple) or a % 2 or b[1] != a + 1:
+                    raise ValueError(f"has an atom at v{a} that is not v{{2i}} OP v{{2i+1}} with OP one of "
+                                     f"{' '.join(SQL_COMPARISONS)}")
+                k = a // 2
+                if k >= n_terms:
+                    raise ValueError(f"names v{a}, Where has {n_terms} terms")
+                if ops[k] is not None:
+                    raise ValueError(f"uses the Where term {k} (v{a}) twice")
+                ops[k] = op
+                operand(sum(1 << m for m in range(1 << n_terms) if m >> k & 1))
+                i += 3
+                want_operand = False
+            else:
+                raise ValueError(f"has {t!r} where an atom, ! or ( is expected")
+        elif t == "&&":
+            i, want_operand = i + 1, True
+        elif t == "||":
+            frame = stack[-1]
+            frame[1], frame[2] = close(frame), []
+            i, want_operand = i + 1, True
+        elif t == ")":
+            if len(stack) == 1:
+                raise ValueError("has unbalanced parentheses: a ) without its (")
+            disj = 0
+            for d in close(stack.pop()):
+                disj |= d
+            operand(disj)
+            i += 1
+        else:
+            raise ValueError(f"has {t if isinstance(t, str) else 'v%d' % t[1]!r} where &&, || or ) is expected")
+    if want_operand:
+        raise ValueError("is empty" if not toks else "ends where an atom is expected")
+    if len(stack) != 1:
+        raise ValueError("has unbalanced parentheses: a ( is never closed")
+    never = [k for k, op in enumerate(ops) if op is None]
+    if never:
+        raise ValueError(f"never uses the Where term {never[0]} (v{2 * never[0]})")
+    table = 0
+    for d in close(stack[0]):
+        table |= d
+    return tuple(ops), table
+
+
 @dataclass
 class SQLPlan:
     """A checked QuerySQL in column indices: ``select`` (the operation's input
     columns; none for a logistic regression), ``where`` [(column, value)],
     ``group_by`` [(column, cardinality)] and the table ``width`` (1 + the
-    largest referenced column)."""
+    largest referenced column).  ``predicate``: None -- a record passes if it
+    equals every ``where`` value -- or ``(ops, table)`` of ``parse_predicate``:
+    term i is the atom ``column ops[i] value`` and a record passes if bit
+    ``sum(atom_i << i)`` of ``table`` is set.  The plain conjunction of
+    equalities is always None."""
     select: list
     where: list
     group_by: list
     width: int
+    predicate: Optional[tuple] = None
 
 
 def sql_plan(q: "Query") -> Optional[SQLPlan]:
@@ -237,8 +376,6 @@ def sql_plan(q: "Query") -> Optional[SQLPlan]:
     if not sql:
         return None
     n_in = max(1, q.Operation.NbrInput)
-    if sql.Predicate:
-        raise ValueError("SQL predicate set: only the conjunction of Where equalities is defined")
     if q.Operation.NameOp == "logistic regression":
         # the columns are those of a DP's key table, beside its float features
         if sql.Select:
@@ -260,6 +397,14 @@ def sql_plan(q: "Query") -> Optional[SQLPlan]:
         if not -(1 << 63) <= int(v) < 1 << 63:
             raise ValueError(f"SQL where value {w.Value!r} is not an int64")
         where.append((col, int(v)))
+    predicate = None
+    if sql.Predicate:
+        try:
+            ops, table = parse_predicate(str(sql.Predicate), len(where))
+        except ValueError as e:
+            raise ValueError(f"SQL predicate {e}; {_NO_PREDICATE}") from None
+        if any(op != "==" for op in ops) or table != 1 << ((1 << len(where)) - 1):
+            predicate = (ops, table)  # the plain conjunction stays None: the plan of the query without a predicate
     group_by = []
     if sql.GroupBy:
         if len(sql.GroupBy) > SQL_MAX_GROUP_BY:
@@ -276,7 +421,7 @@ def sql_plan(q: "Query") -> Optional[SQLPlan]:
         if total > SQL_MAX_GROUPS:
             raise ValueError(f"SQL group by over {total} groups (at most {SQL_MAX_GROUPS})")
     width = 1 + max(select + [c for c, _ in where] + [c for c, _ in group_by])
-    return SQLPlan(select, where, group_by, width)
+    return SQLPlan(select, where, group_by, width, predicate)
 
 
 @dataclass

@@ -6,7 +6,13 @@ verifiable grouped mean against the replicated one.  GPU only; one process.
    d = 8), G = 1 / 6 / 1024 groups (no key, keys of 3 x 2 and of 32 x 32 values,
    uniform) and 0 / 2 filter terms (each passed by half of the rows).  Device
    events around ``--iters`` calls after a warm-up, ``--windows`` windows per
-   case, the cases of one shape alternating.
+   case, the cases of one shape alternating.  ``--predicate FORMULA``
+   (repeatable) adds, per G, the case of that ``QuerySQL.Predicate`` formula
+   over the first n of the terms ``PREDICATE_TERMS`` (n from the formula's
+   highest variable; the first two are the terms of the 2-filter case, the
+   other six hold for every row whatever the comparison ``>=`` (terms 2..5) or
+   ``<=`` (terms 6, 7)), after a check that ``!(v0 != v1) && !(v2 != v3)``
+   gives the 2-filter case's bits: the same rows through the general path.
 2. ``native.int_moments`` (K14, untouched by the grouped kernel: the same code
    as without it) on the same value matrix in the same alternation, for the
    G = 1, no-filter case: what grouping costs when it is not used.
@@ -24,6 +30,7 @@ import argparse
 import copy
 import json
 import os
+import re
 import statistics
 import sys
 import tempfile
@@ -37,13 +44,26 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from drynx_amd import native as nt  # noqa: E402
 from drynx_amd.ops.encoding import moment_pairs  # noqa: E402
-from drynx_amd.query import QuerySQL, new_survey_id  # noqa: E402
+from drynx_amd.query import QuerySQL, new_survey_id, parse_predicate  # noqa: E402
 from drynx_amd.services.api import DrynxClient  # noqa: E402
 from drynx_amd.services.local import local_cluster, make_survey  # noqa: E402
 
 SHAPES = {1: "mean", 2: "cosim", 9: "lin_reg"}  # value columns -> the operation whose pairs are summed
 GROUPS = {1: [], 6: [(0, 0, 3), (1, 0, 2)], 1024: [(2, 0, 32), (3, 0, 32)]}
 FILTERS = {0: [], 2: [(4, 1), (5, 0)]}
+# the Where terms of --predicate: the two of FILTERS[2], then six that every row passes with >= (2..5) or <= (6, 7)
+PREDICATE_TERMS = FILTERS[2] + [(0, 0), (1, 0), (2, 0), (3, 0), (4, 1), (5, 1)]
+
+
+def predicate_case(formula: str):
+    """(filters, (ops, table)) of a --predicate formula over the first terms of PREDICATE_TERMS."""
+    n = 1 + max([int(v) for v in re.findall(r"v(\d+)", formula)] or [0]) // 2
+    if n > len(PREDICATE_TERMS):
+        sys.exit(f"bench_groupby: --predicate {formula!r} names more than {len(PREDICATE_TERMS)} terms")
+    try:
+        return PREDICATE_TERMS[:n], parse_predicate(formula, n)
+    except ValueError as e:
+        sys.exit(f"bench_groupby: --predicate {formula!r} {e}")
 
 
 def window(f, iters, device) -> float:
@@ -72,11 +92,20 @@ def encoder_alone(args, device) -> dict:
         for G, keys in GROUPS.items():
             for nf, filters in FILTERS.items():
                 calls[f"G={G},filters={nf}"] = (lambda k=keys, f=filters: nt.group_moments(Z, K, rows, pairs, k, f))
+            for formula in args.predicate:
+                filters, pred = predicate_case(formula)
+                calls[f"G={G},predicate={formula}"] = (
+                    lambda k=keys, f=filters, p=pred: nt.group_moments(Z, K, rows, pairs, k, f, predicate=p))
         # results must agree before anything is timed
         whole = nt.int_moments(Z, rows, pairs)
         assert torch.equal(calls["G=1,filters=0"]()[:, 0], whole)
         assert torch.equal(calls["G=6,filters=0"]().sum(1), whole) and torch.equal(calls["G=1024,filters=0"]().sum(1),
                                                                                    whole)
+        if args.predicate:  # the equalities through the general path: the 2-filter case's bits
+            same = parse_predicate("!(v0 != v1) && !(v2 != v3)", 2)
+            for G, keys in GROUPS.items():
+                assert torch.equal(nt.group_moments(Z, K, rows, pairs, keys, FILTERS[2], predicate=same),
+                                   calls[f"G={G},filters=2"]())
         ms = {k: [] for k in calls}
         for f in calls.values():
             for _ in range(5):
@@ -146,6 +175,9 @@ def main():
     ap.add_argument("--steps", type=int, default=5, help="timed queries per run")
     ap.add_argument("--passes", type=int, default=3, help="times the grouped / replicated pair is gone through")
     ap.add_argument("--no-query", action="store_true", help="the encoder alone")
+    ap.add_argument("--predicate", action="append", default=[],
+                    help="a QuerySQL.Predicate formula over the first terms of PREDICATE_TERMS: one more encoder "
+                         "case per G (repeatable)")
     ap.add_argument("--out-dir", default=None, help="write groupby.json here")
     args = ap.parse_args()
     if not torch.cuda.is_available():

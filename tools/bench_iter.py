@@ -29,15 +29,18 @@ atomics of a workgroup on one counter).
 
 ``--groups V`` runs the searches over SQL cohorts: every DP holds a table (x,
 c1 uniform in [0, V), c2 uniform in [0, 3]), the survey carries ``GROUP BY c1``
-(and ``--where c2=1`` a WHERE term), and one walk finds the quantile or max of
-every cell (``SurveyQuery.IterPrefixes``).  A result is right when every cell's
+(and ``--where c2=1`` a WHERE term, ``--predicate 'v0 >= v1'`` a
+``QuerySQL.Predicate`` formula over that one term), and one walk finds the
+quantile or max of every cell (``SurveyQuery.IterPrefixes``).  A result is right when every cell's
 value equals the clear one of the redrawn tables (NaN, or the one-shot empty
 value QueryMin for ``max``, for a cell without records).  The one-shot SQL query
 alternates where V * N <= 100000.  The encoder alone is then the grouped digit
 histogram ``native.iter_round_cells`` for V in {1, 16, 256, 4096} at base 10 and
 1000, uniform keys against every row in one cell and one bin, beside
 ``native.iter_round`` on the same records and ``native.group_moments(...,
-bins=...)`` on the last-round shape.
+bins=...)`` on the last-round shape; with ``--where`` also the uniform case
+under that equality (``uniform_where``) and with ``--predicate`` under the
+formula (``uniform_predicate``), on a table with the column c2.
 
 ``--gpus W`` (W > 1) starts W ranks; the ranks without the querier serve the
 rounds (``serve_iterative``).  Prints one JSON object; ``--out-dir`` also
@@ -64,7 +67,7 @@ import bench  # noqa: E402  (the max configuration, the reference rows, the laun
 from drynx_amd import native as nt  # noqa: E402
 from drynx_amd.ops import encoding as enc  # noqa: E402
 from drynx_amd.parallel.comm import init_distributed, make_comm  # noqa: E402
-from drynx_amd.query import QuerySQL, WhereClear, iter_rounds, new_survey_id  # noqa: E402
+from drynx_amd.query import QuerySQL, WhereClear, iter_rounds, new_survey_id, parse_predicate  # noqa: E402
 from drynx_amd.rounds import ITER_MAX_CELL_OUTPUTS, ITER_MAX_HIST_BASE, max_base  # noqa: E402
 from drynx_amd.services.api import DrynxClient, serve_iterative  # noqa: E402
 from drynx_amd.services.local import local_cluster, make_iterative_survey, make_survey  # noqa: E402
@@ -90,6 +93,8 @@ def parse():
     ap.add_argument("--no-classic", action="store_true", help="skip the one-shot query")
     ap.add_argument("--groups", type=int, default=0, help="V > 0: GROUP BY c1 over V groups, one search per cell")
     ap.add_argument("--where", default=None, help="with --groups: a WHERE term c2=<0..3> (e.g. c2=1)")
+    ap.add_argument("--predicate", default="",
+                    help="with --where: a QuerySQL.Predicate formula over the one term, e.g. 'v0 >= v1'")
     ap.add_argument("--encoder-iters", type=int, default=200, help="encoder calls per timed window (GPU only)")
     ap.add_argument("--out-dir", default=None, help="write range_<N>.json here")
     ap.set_defaults(cns=3, dps=10, vns=3)
@@ -106,6 +111,14 @@ def parse():
         if not args.groups or col != "c2" or not val.isdigit():
             ap.error("--where c2=<value> goes with --groups")
         args.where_value = int(val)
+    args.where_predicate = None
+    if args.predicate:
+        if args.where_value is None:
+            ap.error("--predicate goes with --where")
+        try:
+            args.where_predicate = parse_predicate(args.predicate, 1)
+        except ValueError as e:
+            ap.error(f"--predicate {e}")
     top = min(max_base(OPERATION[args.query]), ITER_MAX_HIST_BASE) if args.groups else max_base(OPERATION[args.query])
     if args.groups < 0 or args.groups > 4096 or any(args.groups * b > ITER_MAX_CELL_OUTPUTS for b in args.base_list):
         ap.error(f"--groups in 1..4096 with groups * base at most {ITER_MAX_CELL_OUTPUTS}")
@@ -247,7 +260,19 @@ COHORT_PROBE_WHAT = ("iter_round_cells('frequencyCount') (one launch per group w
                      "the last-round shape (V x base cells); device events, three windows each, alternating")
 
 
-def cohort_probe_cases(rows, g, device):
+def passes_where(args, c2: int) -> bool:
+    """Does a record with this c2 pass --where / --predicate (the one atom's bit indexes the truth table)?"""
+    if args.where_value is None:
+        return True
+    if args.where_predicate is None:
+        return c2 == args.where_value
+    (op,), table = args.where_predicate
+    atom = {"==": c2 == args.where_value, "!=": c2 != args.where_value, "<": c2 < args.where_value,
+            "<=": c2 <= args.where_value, ">": c2 > args.where_value, ">=": c2 >= args.where_value}[op]
+    return bool(table >> int(atom) & 1)
+
+
+def cohort_probe_cases(rows, g, device, where_value=None, predicate=None):
     n = sum(rows)
     for b in (10, 1000):
         R = b ** 2
@@ -265,6 +290,13 @@ def cohort_probe_cases(rows, g, device):
             calls = {"uniform": cells(Ku), "one_cell_one_bin": cells(Ke),
                      "group_moments_bins": lambda K=Ku, keys=keys, b=b: nt.group_moments(
                          K[:, :0], K, rows, [(0, 0)], keys, bins=(0, 0, b))}
+            if where_value is not None:  # the same rows and keys with the filter column c2 in [0, 3]
+                Kf = torch.cat([Ku, torch.randint(0, 4, (n, 1), generator=g, device=device)], dim=1)
+                calls["uniform_where"] = lambda K=Kf, keys=keys, zero=zero, b=b, R=R: nt.iter_round_cells(
+                    "frequencyCount", K, rows, 0, 0, R - 1, b, 0, zero, keys, [(2, where_value)])
+                if predicate is not None:
+                    calls["uniform_predicate"] = lambda K=Kf, keys=keys, zero=zero, b=b, R=R: nt.iter_round_cells(
+                        "frequencyCount", K, rows, 0, 0, R - 1, b, 0, zero, keys, [(2, where_value)], predicate)
             if V == 1:
                 calls["iter_round"] = lambda K=Ku, b=b, R=R: nt.iter_round("frequencyCount", K, rows, 0, R - 1, b, 0, 0)
                 calls["iter_round_one_bin"] = lambda K=Ke, b=b, R=R: nt.iter_round("frequencyCount", K, rows, 0, R - 1,
@@ -278,7 +310,9 @@ def encoder_alone(args, query, device) -> dict:
     rows = [100_000] * 10
     out = {"records": "10 DPs x 100000", "calls_per_window": args.encoder_iters,
            "what": COHORT_PROBE_WHAT if args.groups else query.probe_what, "ms_per_call": {}}
-    for label, calls in (cohort_probe_cases if args.groups else query.probe_cases)(rows, g, device):
+    cases = cohort_probe_cases(rows, g, device, args.where_value, args.where_predicate) if args.groups else \
+        query.probe_cases(rows, g, device)
+    for label, calls in cases:
         ms = {k: [] for k in calls}
         for f in calls.values():
             for _ in range(5):
@@ -324,10 +358,10 @@ def main():
                      torch.randint(0, 4, (rows,), generator=g, device=device)]
         mine = [r for cols in node.dp_data.values() for r in torch.stack(cols, dim=1).cpu().tolist()]
         table = [r for part in comm.all_gather_object(mine) for r in part]
-        keep = [r for r in table if args.where_value is None or r[2] == args.where_value]
+        keep = [r for r in table if passes_where(args, r[2])]
         want = [query.clear_cell([x for x, c1, _ in keep if c1 == c]) for c in range(V)]
         where = [] if args.where_value is None else [WhereClear("c2", str(args.where_value))]
-        sql_kw = {"group_by": (V,), "sql": QuerySQL(Where=where, GroupBy=["c1"])}
+        sql_kw = {"group_by": (V,), "sql": QuerySQL(Where=where, Predicate=args.predicate, GroupBy=["c1"])}
     else:
         want = query.clear(comm, [int(x) for cols in node.dp_data.values() for x in cols[0].cpu().tolist()])
 
@@ -422,7 +456,7 @@ def main():
         return
     out = {"tool": "bench_iter", "query": args.query, "range": N, "steps_per_run": args.steps, "n_gpus": world,
            "device": device.type, "order": [r["query"] for r in runs], **query.head(N, want),
-           **({"groups": V, "where": args.where} if V else {}),
+           **({"groups": V, "where": args.where, "predicate": args.predicate} if V else {}),
            "config": {"cns": args.cns, "vns": args.vns, "dps": n_dps, "records_per_dp": rows,
                       "range_proof": query.range_proof, "sigs": "random (per CN, per column)",
                       "thresholds": [1, 1, 1, 0, 1]},

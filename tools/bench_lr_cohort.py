@@ -12,6 +12,9 @@ process.
    of one size alternating.  The G = 1 result is checked against
    ``lr_encode_many`` (the same bits) and every grouped result against it
    (the cells sum to the whole within rounding) before anything is timed.
+   ``--predicate FORMULA``: one more case per G, the ``QuerySQL.Predicate``
+   formula over the two terms of the quarter Where (``!(v0 != v1) && !(v2 !=
+   v3)`` passes the quarter's rows through the general rule).
 2. A verifiable ``logistic regression`` with (16, 5, offset 2^19) range proofs
    over 10 DPs x 10,000 records, d = 8, 3 CNs and 3 VNs: ``GroupBy = [c0, c1]``
    with 3 x 2 real cohorts against the same query without SQL and
@@ -39,7 +42,7 @@ import torch  # noqa: E402
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from drynx_amd import native as nt  # noqa: E402
-from drynx_amd.query import LogisticRegressionParameters, QuerySQL, new_survey_id  # noqa: E402
+from drynx_amd.query import LogisticRegressionParameters, QuerySQL, new_survey_id, parse_predicate  # noqa: E402
 from drynx_amd.services.api import DrynxClient  # noqa: E402
 from drynx_amd.services.local import local_cluster, make_survey  # noqa: E402
 
@@ -72,6 +75,12 @@ def encoder_alone(args, device, n) -> dict:
             calls[f"G={G},{fname}"] = (lambda k=keys, f=filters:
                                        nt.lr_encode_cells_many([X], [y], [K], m, s, -1.0, k, f))
             calls[f"plan G={G},{fname}"] = (lambda k=keys, f=filters: nt.lr_cell_plan(K, n, k, f))
+        if args.predicate:
+            pred = parse_predicate(args.predicate, 2)
+            calls[f"G={G},predicate"] = (lambda k=keys, p=pred: nt.lr_encode_cells_many(
+                [X], [y], [K], m, s, -1.0, k, FILTERS["quarter"], predicate=p))
+            calls[f"plan G={G},predicate"] = (lambda k=keys, p=pred: nt.lr_cell_plan(K, n, k, FILTERS["quarter"],
+                                                                                  predicate=p))
     whole = calls["lr_encode_many"]()
     assert torch.equal(calls["G=1,all"]()[:, 0], whole)
     for G in GROUPS:
@@ -151,6 +160,8 @@ def main():
     ap.add_argument("--steps", type=int, default=3, help="timed queries per run")
     ap.add_argument("--passes", type=int, default=3, help="times the cohorts / replicated pair is gone through")
     ap.add_argument("--no-query", action="store_true", help="the encoder alone")
+    ap.add_argument("--predicate", default="",
+                    help="a QuerySQL.Predicate formula over the two terms of the quarter Where: one more case per G")
     ap.add_argument("--out-dir", default=None, help="write lr_cohort.json here")
     args = ap.parse_args()
     if not torch.cuda.is_available():
