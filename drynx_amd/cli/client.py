@@ -75,6 +75,62 @@ def where_terms(terms, predicate: str):
     return where, predicate or ""
 
 
+def kmeans_centroids(text: str, k: int, d: int, qmin: int, scale: int) -> list:
+    """``--centroids "x,y;x,y"``: k points of d coordinates in record units ->
+    the k * d scaled offsets (x - qmin) * scale, which must be whole."""
+    from fractions import Fraction
+
+    pts = [[v.strip() for v in pt.split(",") if v.strip()] for pt in text.split(";") if pt.strip()]
+    if len(pts) != k or any(len(pt) != d for pt in pts):
+        raise SystemExit(f"--centroids {text}: expected {k} points of {d} coordinates, as in \"x,y;x,y\"")
+    out = []
+    for pt in pts:
+        for v in pt:
+            try:
+                c = (Fraction(v) - qmin) * scale
+            except (ValueError, ZeroDivisionError):
+                raise SystemExit(f"--centroids {text}: {v} is not a number")
+            if c.denominator != 1:
+                raise SystemExit(f"--centroids {text}: {v} is not a multiple of 1/{scale} (--scale)")
+            out.append(int(c))
+    return out
+
+
+def survey_run_kmeans(a, cfg, client, sq):
+    """``survey set-operation kmeans`` ... ``survey run --clusters K --dims D
+    --rounds N [--scale S] [--centroids "x,y;x,y"]``: K clusters of the DPs'
+    records (their first D columns, over [0, 256]) in N verifiable rounds.
+    The default start centroids are ``kmeans.random_centroids`` seeded from the
+    survey name.  Prints one line per cluster: its index, the records the last
+    round assigned to it, and its centroid in record units."""
+    from .. import kmeans as km
+    from ..query import KMeansParameters, check_parameters, kmeans_operation
+
+    if a.group_by or a.cardinalities or a.where or a.predicate or a.select:
+        raise SystemExit("kmeans over SQL cohorts is not defined: no --group-by, --where, --predicate or --select")
+    if a.clusters is None or a.dims is None or a.rounds is None:
+        raise SystemExit("kmeans needs --clusters K --dims D --rounds N")
+    g = sq.Query.DPDataGen
+    try:
+        op = kmeans_operation(g.GenerateDataMin, g.GenerateDataMax, a.dims, a.clusters)
+        km.check(a.clusters, a.dims, op.QueryMin, op.QueryMax, a.scale)
+        km.check_rounds(a.rounds)
+    except ValueError as e:
+        raise SystemExit(str(e))
+    R = op.QueryMax - op.QueryMin + 1
+    if a.centroids:
+        start = kmeans_centroids(a.centroids, a.clusters, a.dims, op.QueryMin, a.scale)
+    else:
+        start = km.random_centroids(a.clusters, a.dims, R, a.scale, cfg["Survey"].get("Name") or "")
+    op.KMeans = KMeansParameters(K=a.clusters, Scale=a.scale, Round=0, Rounds=a.rounds, Centroids=start)
+    sq.Query.Operation = op
+    if not check_parameters(sq, False):
+        raise SystemExit("the k-means query is not valid (see the log)")
+    res = client.send_kmeans(sq, start)
+    for c, (n, pt) in enumerate(zip(res.counts, res.points)):
+        print(f"{c}: {n}: " + " ".join(str(float(x)) for x in pt))
+
+
 def survey_run(a):
     """roster[0] is the CN (and the VN roster), roster[1:] are DPs; no proofs;
     GroupBy {3,2,1}; 10 rows in [0, 256] (survey.go:93-132).  ``--group-by c1,c3
@@ -103,10 +159,13 @@ def survey_run(a):
     id_to_pub = {f"cn:{cn}": pubs[cn], f"vn:{cn}": pubs[cn]}
     id_to_pub.update({f"dp:{d}": pubs[d] for d in dps})
     s2dp = {f"cn:{cn}": [ServerIdentity(f"dp:{d}", pubs[d], d, i + 1) for i, d in enumerate(dps)]}
-    op = choose_operation(cfg["Survey"]["Operation"], 0, 256, 5, 0)
+    kmeans = cfg["Survey"]["Operation"] == "kmeans"  # its operation is survey_run_kmeans' to build
+    op = choose_operation("sum" if kmeans else cfg["Survey"]["Operation"], 0, 256, 5, 0)
     client = DrynxClient(RemoteNode(entry))  # the roster travels inside the SurveyQuery
     sq = client.generate_survey_query(roster, None, s2dp, id_to_pub, cfg["Survey"].get("Name"), op, None, None, 0,
                                       False, [0.0] * 5, QueryDiffP(), QueryDPDataGen([3, 2, 1], 10, 0, 256))
+    if kmeans:
+        return survey_run_kmeans(a, cfg, client, sq)
     csv = lambda v: [x.strip() for x in (v or "").split(",") if x.strip()]  # noqa: E731
     sq.Query.SQL = QuerySQL(Select=csv(a.select), Where=where, Predicate=predicate, GroupBy=csv(a.group_by))
     if sq.Query.SQL.GroupBy:
@@ -158,6 +217,12 @@ def main(argv=None):
                    help="a formula over the --where terms, v{2i} the column and v{2i+1} the value of term i, "
                         "e.g. 'v0 == v1 || !(v2 == v3)'")
     p.add_argument("--select", default="", help="the operation's input columns, e.g. c0")
+    p.add_argument("--clusters", type=int, help="kmeans: the number of clusters K")
+    p.add_argument("--dims", type=int, help="kmeans: the columns D of a record")
+    p.add_argument("--rounds", type=int, help="kmeans: the number of rounds N")
+    p.add_argument("--scale", type=int, default=1, help="kmeans: centroids move in steps of 1/SCALE (default 1)")
+    p.add_argument("--centroids", default="", help="kmeans: the K start points, e.g. \"10,20;200,40\" "
+                                                     "(default: drawn from the survey name)")
     p.set_defaults(fn=survey_run)
     a = ap.parse_args(argv)
     a.fn(a)

@@ -24,6 +24,7 @@ import numpy as np
 
 import torch
 
+from .. import kmeans as km
 from .. import rounds
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -149,6 +150,8 @@ _SIGS = {
     "dx_group_moments_pred": [_I, _P, _P, _L, _I, _P, _L, _I, _P, _L, _P, _I, _P, _I, _P, _I, _L, _L, _P, _P],
     "dx_group_moments_max_cells": [],
     "dx_group_cells": [_I, _P, _P, _L, _I, _L, _P, _I, _P, _I, _P],
+    "dx_kmeans_round": [_I, _P, _P, _L, _P, _L, _L, _P, _L, _L, _L, _L, _L, _P],
+    "dx_kmeans_max_cells": [],
     "dx_group_cells_pred": [_I, _P, _P, _L, _I, _L, _P, _I, _P, _I, _P, _P],
     "dx_sha256_rows": [_I, _P, _P, _L, _L, _L, _L, _P],
     "dx_sha256_segments": [_I, _P, _P, _L, _L, _L, _P],
@@ -1439,6 +1442,53 @@ def iter_round_cells(name: str, K: torch.Tensor, seg_rows, xcol: int, qmin: int,
         if rc != 0:
             raise RuntimeError(f"native op dx_iter_round_cells failed (rc={rc})")
     return rows_of_counts(name, out)
+
+
+def kmeans_round(Z: torch.Tensor, seg_rows, d: int, k: int, qmin: int, qmax: int, scale: int,
+                 centroids) -> torch.Tensor:
+    """K14f (csrc/kernels/dx_kmeans.hip): the [n_dp, k * (d + 2)] int64 rows every
+    DP of a batch encrypts in one round of a k-means query (``drynx_amd.kmeans``).
+
+    Z [rows, >= d] holds the DPs' records back to back (``seg_rows[g]`` rows for
+    DP g; columns 0 .. d-1 are read in place through Z's row stride, a column
+    view of a wider table is fine).  A row with a coordinate outside [qmin,
+    qmax] is dropped; a kept row with the offsets o_j = x_j - qmin goes to the
+    cluster c with the smallest sum_j (scale * o_j - centroids[c * d + j])^2,
+    the lowest index among equals; row g is cluster-major [n_c, sum o_0 .. sum
+    o_(d-1), sum |o|^2] over DP g's kept rows (``kmeans.round_model``).  One
+    launch for all DPs, one upload for the tile plan and the centroids, no torch
+    op and no host work per record; the tiles stream at least as many rows as
+    they zero and flush cells."""
+    assert Z.dtype == torch.int64 and Z.dim() == 2 and (Z.shape[1] <= 1 or Z.stride(1) == 1)
+    cen = [int(c) for c in centroids]
+    km.check(k, d, qmin, qmax, scale, cen)
+    counts = np.asarray(seg_rows, dtype=np.int64).reshape(-1)
+    n_dp = len(counts)
+    if counts.sum() != Z.shape[0] or (n_dp and counts.min() < 0):
+        raise ValueError(f"k-means: segments cover {counts.sum()} rows, Z has {Z.shape[0]}")
+    if Z.shape[0] and Z.shape[1] < d:
+        raise ValueError(f"k-means: Z has {Z.shape[1]} columns, the query reads {d}")
+    cells = k * (d + 2)
+    out = torch.zeros((n_dp, cells), dtype=torch.int64, device=Z.device)
+    plan, _ = _tile_plan(counts, min(cells, 2048))
+    n_tiles = len(plan)
+    if n_tiles == 0:
+        return out
+    if Z.device.type == "cuda":
+        no_capture("kmeans_round")
+    if qmax == qmin:
+        scale = 1  # one value: every offset and every centroid is 0, whatever the scale
+    # one upload: the tiles, then the centroids
+    desc = _upload(np.concatenate([plan.reshape(-1), np.asarray(cen, dtype=np.int64)]), Z.device)
+    g, s = _ctx(Z, out)
+    rc = _raw_call("dx_kmeans_round", g, s, _ptr(Z, strided=True), Z.stride(0) if Z.shape[0] > 1 else max(1, d),
+                   _ptr(desc[: 3 * n_tiles]), n_tiles, n_dp, _ptr(desc[3 * n_tiles:]), k, d, scale, qmin, qmax,
+                   _ptr(out))
+    if rc == -2:
+        raise ValueError("k-means: the entry refused its arguments")
+    if rc != 0:
+        raise RuntimeError(f"native op dx_kmeans_round failed (rc={rc})")
+    return out
 
 
 def sha256_rows(data: torch.Tensor, chunk: int) -> torch.Tensor:

@@ -324,6 +324,35 @@ def encode_iterative(data, operation: Operation, base: int, rnd: int, prefix: in
     return encode_bits([v == 0 for v in vals], pk, "and", with_proofs, ranges)  # values are the inverted AND bits
 
 
+def kmeans_values(operation: Operation, Z: torch.Tensor, seg_rows) -> torch.Tensor:
+    """[n_dp, K * (d + 2)] int64 values of one round of a k-means query
+    (``Operation.KMeans``, ``drynx_amd.kmeans``): per DP and cluster the count,
+    the d coordinate sums and the sum of squares of the records the round's
+    centroids assign to it; records outside the domain are dropped.  Z [rows,
+    >= d] stacks the DPs' records, its first d = NbrInput columns are read in
+    place.  One launch for every DP of the batch (``native.kmeans_round``); the
+    host path runs the same entry."""
+    from .. import native as nt
+
+    p = operation.KMeans
+    if operation.NameOp != "kmeans" or p is None:
+        raise ValueError(f"{operation.NameOp} is not a round of a k-means query")
+    return nt.kmeans_round(Z, seg_rows, operation.NbrInput, p.K, operation.QueryMin, operation.QueryMax, p.Scale,
+                           p.Centroids)
+
+
+def encode_kmeans(data, operation: Operation, pk, with_proofs=False, ranges=None):
+    """One DP's response to one round of a k-means query: the values of
+    ``kmeans_values`` for its records (``data``: the d column tensors),
+    encrypted as integers like ``encode_frequency_count``'s."""
+    d = operation.NbrInput
+    if len(data) < d:
+        raise ValueError(f"a k-means round reads {d} columns, the DP has {len(data)}")
+    Z = torch.stack([_t(c, pk.device).reshape(-1).to(torch.int64) for c in data[:d]], dim=1)
+    vals = kmeans_values(operation, Z, [Z.shape[0]])[0].cpu().tolist()
+    return _encrypt_with_proofs(pk, vals, with_proofs, ranges)
+
+
 def encrypt_batch(pk: eg.PublicKeyTable, values: torch.Tensor, bits: bool):
     """One encryption launch for a whole batch: ints (EncryptIntVectorGetRs),
     or for bit encodings without proofs a fresh random non-zero scalar where the
@@ -421,6 +450,8 @@ def encode(datas, pk: eg.PublicKeyTable, operation: Operation, ranges=None, with
         return encode_inter(datas, qmin, qmax, pk, with_proofs, ranges)
     if name == "MLeval":
         return encode_model_evaluation(datas, pk, with_proofs, ranges)
+    if name == "kmeans":
+        return encode_kmeans(datas, operation, pk, with_proofs, ranges)
     if name == "logistic regression":
         from ..models.logistic_regression import encode_logistic_regression
 

@@ -52,7 +52,12 @@ def data_seed_id(sq) -> str:
     """The id a DP's generated records are seeded from: the survey's, or for a
     round of an iterative query the id its rounds share (every round has a
     survey id of its own and must still see the same records)."""
-    return sq.IterSurveyID if sq.IterBase else sq.SurveyID
+    if sq.IterBase:
+        return sq.IterSurveyID
+    op = sq.Query.Operation
+    if op.NameOp == "kmeans" and op.KMeans is not None:  # the rounds of a k-means run share KMeans.SearchID
+        return op.KMeans.SearchID
+    return sq.SurveyID
 
 
 def generate_fake_data(op, nbr_rows: int, lo: int, hi: int, device, gen: torch.Generator):
@@ -207,6 +212,10 @@ def dp_encode_batch(ctx, sq, dps: list) -> dict:
         vals = enc.batch_values_sql(op.NameOp, Zv, Z, rows, plan, op.QueryMin, op.QueryMax)
     elif sq.IterBase:  # one round of an iterative query: [n_dp, IterBase] from the K14b (min/max) or K14c (counts) pair
         vals = enc.iterative_values(op, Z, rows, sq.IterBase, sq.IterRound, sq.IterPrefix)
+    elif op.NameOp == "kmeans":  # one round of a k-means query: [n_dp, K * (d + 2)] from K14f, Z's first d columns
+        if Z.shape[1] < n_in:
+            raise ValueError(f"a k-means round reads {n_in} columns, the DPs' records have {Z.shape[1]}")
+        vals = enc.kmeans_values(op, Z[:, :n_in], rows)
     else:
         vals = enc.batch_values(op.NameOp, Z, rows, op.QueryMin, op.QueryMax)  # [n_dp, n_out]
     return _encode_batch_tail(ctx, sq, dps, vals, groups, pk)
@@ -344,7 +353,7 @@ def data_collection(ctx, sq) -> tuple:
     # the per-DP timer syncs the device only for a handful of DPs per rank: with
     # thousands (ScaleDPs, one record each) the syncs serialise the encoders
     sync_timer = len(local_dps) <= 16
-    batchable = sq.Query.Operation.NameOp in enc.BATCH_OPS + ("logistic regression",)
+    batchable = sq.Query.Operation.NameOp in enc.BATCH_OPS + ("logistic regression", "kmeans")
     abort = None
     try:
         if local_dps and batchable:

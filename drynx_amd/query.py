@@ -17,6 +17,7 @@ import uuid
 from dataclasses import dataclass, field, fields, is_dataclass
 from typing import Optional
 
+from . import kmeans as km
 from .crypto import oracle as O
 from .rounds import (ITER_MAX_BASE, ITER_MAX_CELL_OUTPUTS, ITER_MAX_HIST_BASE, ITER_MAX_RANGE,  # re-exported
                      ITER_OPERATIONS, iter_rounds)
@@ -145,6 +146,23 @@ class LogisticRegressionParameters:
 
 
 @dataclass
+class KMeansParameters:
+    """extension: one round of a k-means query (``drynx_amd.kmeans``, the
+    operation ``kmeans``).  The records have NbrInput = d columns over
+    [QueryMin, QueryMax]; ``Centroids`` are the K * d coordinates the round
+    assigns by, cluster-major, integers in units of 1 / ``Scale``; ``Round`` of
+    ``Rounds`` counts from 0.  ``SearchID`` is the id the rounds of one run
+    share: generated records are seeded from it, so every round sees the same
+    data."""
+    K: int = 0
+    Scale: int = 1
+    Round: int = 0
+    Rounds: int = 1
+    Centroids: list = field(default_factory=list)
+    SearchID: str = ""
+
+
+@dataclass
 class Operation:
     NameOp: str = ""
     NbrInput: int = 0
@@ -152,6 +170,7 @@ class Operation:
     QueryMin: int = 0
     QueryMax: int = 0
     LRParameters: LogisticRegressionParameters = field(default_factory=LogisticRegressionParameters)
+    KMeans: Optional[KMeansParameters] = None  # set for the operation "kmeans" only
 
 
 @dataclass
@@ -545,6 +564,8 @@ def _to_jsonable(obj):
                 continue  # an empty SQL is the dict of a query without the field
             elif f.name == "IterPrefixes" and not v:
                 continue  # likewise: the dict of every survey without cell prefixes is unchanged
+            elif f.name == "KMeans" and v is None:
+                continue  # and the dict of every operation but k-means
             else:
                 out[f.name] = _to_jsonable(v)
         return out
@@ -565,10 +586,21 @@ def sql_from_dict(d) -> QuerySQL:
                     GroupBy=[str(s) for s in d.get("GroupBy") or []])
 
 
+def kmeans_from_dict(d) -> Optional[KMeansParameters]:
+    """KMeansParameters of their dict (JSON control plane or decoded wire
+    message); a peer without the block (None) reads as no k-means."""
+    if d is None:
+        return None
+    return KMeansParameters(K=int(d.get("K") or 0), Scale=int(d.get("Scale") or 0), Round=int(d.get("Round") or 0),
+                            Rounds=int(d.get("Rounds") or 0), Centroids=[int(c) for c in d.get("Centroids") or []],
+                            SearchID=str(d.get("SearchID") or ""))
+
+
 def _survey_from_dict(d: dict) -> SurveyQuery:
     q = d["Query"]
     op = dict(q["Operation"])
     op["LRParameters"] = LogisticRegressionParameters(**op.get("LRParameters", {}))
+    op["KMeans"] = kmeans_from_dict(op.get("KMeans"))
     ivs = dict(q.get("IVSigs") or {})
     if ivs.get("InputValidationSigs") is not None:
         ivs["InputValidationSigs"] = [[PublishSignatureBytes.from_dict(s) for s in row]
@@ -684,6 +716,7 @@ def check_parameters(sq: SurveyQuery, diffp: bool) -> bool:
                 msg.append("initial weights are neither empty, one vector of d + 1 nor one per target")
     msg += _check_iterative(sq)
     msg += _check_sql(sq)
+    msg += _check_kmeans(sq)
     if q.Operation.QueryMin != q.DPDataGen.GenerateDataMin or q.Operation.QueryMax != q.DPDataGen.GenerateDataMax:
         msg.append("min or max are inconsistent at DP and operations")
     for m in msg:
@@ -733,6 +766,44 @@ def _check_iterative(sq: SurveyQuery) -> list:
             msg.append("an iterative frequencyCount round with (0, 0) among other ranges")
     elif q.Proofs and (q.Ranges is None or not _ranges_bits(q.Ranges)):
         msg.append("iterative rounds with proofs need (2, 1) ranges")
+    return msg
+
+
+def _check_kmeans(sq: SurveyQuery) -> list:
+    """Rules of a round of a k-means query (``Operation.KMeans``); nothing for
+    every other operation without the block."""
+    q = sq.Query
+    op = q.Operation
+    p = op.KMeans
+    if op.NameOp != "kmeans":
+        return [] if p is None else [f"k-means parameters with the operation {op.NameOp}"]
+    if p is None:
+        return ["k-means without its parameters (Operation.KMeans)"]
+    try:
+        km.check(p.K, op.NbrInput, op.QueryMin, op.QueryMax, p.Scale,
+                 p.Centroids if isinstance(p.Centroids, (list, tuple)) else None)
+        if not isinstance(p.Centroids, (list, tuple)):
+            raise ValueError("k-means: the centroids are not a list")
+        km.check_rounds(p.Rounds, p.Round)
+    except ValueError as e:
+        return [str(e)]
+    msg = []
+    n_out = p.K * (op.NbrInput + 2)
+    if op.NbrOutput != n_out:
+        msg.append(f"a k-means round has exactly K * (d + 2) = {n_out} outputs")
+    if sq.IterBase:
+        msg.append("k-means with iterative digits (IterBase): its rounds are KMeans.Round")
+    if q.CuttingFactor != 0:
+        msg.append("k-means with a cutting factor")
+    if add_diff_p(q.DiffP):
+        msg.append("k-means with differential privacy")
+    if q.Obfuscation:
+        msg.append("k-means with obfuscation")
+    # counts and sums, not bits: any range wide enough for a DP's records, one per output
+    if q.Proofs and (q.Ranges is None or len(q.Ranges) != n_out):
+        msg.append(f"a k-means round with proofs needs one range per output ({n_out})")
+    elif q.Proofs and any(r[0] == 0 and r[1] == 0 for r in q.Ranges):
+        msg.append("a k-means round with a (0, 0) range")
     return msg
 
 
@@ -862,6 +933,18 @@ def iter_operation(name: str, query_min: int, query_max: int, base: int) -> Oper
         raise ValueError(f"Operation: <{name}> has no iterative rounds")
     iter_rounds(query_min, query_max, base)
     return Operation(NameOp=name, NbrInput=1, NbrOutput=int(base), QueryMin=int(query_min), QueryMax=int(query_max))
+
+
+def kmeans_operation(query_min: int, query_max: int, d: int, k: int) -> Operation:
+    """The operation of one round of a k-means query (extension): ``d`` input
+    columns over [query_min, query_max], k * (d + 2) outputs (per cluster the
+    count, the d coordinate sums and the sum of squares).  The round's
+    parameters (``Operation.KMeans``) are the sender's to set."""
+    d, k = int(d), int(k)
+    if not 1 <= d <= km.KMEANS_MAX_DIMS or not 1 <= k <= km.max_clusters(d):
+        raise ValueError(f"Operation: <kmeans> over {d} columns has no {k} clusters")
+    return Operation(NameOp="kmeans", NbrInput=d, NbrOutput=k * (d + 2), QueryMin=int(query_min),
+                     QueryMax=int(query_max))
 
 
 MAX_LR_TARGETS = 64

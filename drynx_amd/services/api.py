@@ -13,12 +13,35 @@ see services/server.py).
 from __future__ import annotations
 
 import copy
+from dataclasses import dataclass, field
 
+from .. import kmeans as km
 from ..crypto import elgamal as eg
 from ..ops import encoding as enc
-from ..query import (LogisticRegressionParameters, Operation, Query, QueryDiffP, QueryDPDataGen, QueryIVSigs, Roster,
-                     SurveyQuery, check_parameters, iter_operation, iter_rounds, new_survey_id, sql_cells, sql_plan)
+from ..query import (KMeansParameters, LogisticRegressionParameters, Operation, Query, QueryDiffP, QueryDPDataGen,
+                     QueryIVSigs, Roster, SurveyQuery, check_parameters, iter_operation, iter_rounds, new_survey_id,
+                     sql_cells, sql_plan)
 from ..utils import timers
+
+
+@dataclass
+class KMeansResult:
+    """What ``DrynxClient.send_kmeans`` returns.  ``centroids``: the final K * d
+    scaled coordinates (the update of the last round run), ``points`` the same
+    as K lists of d Fractions in record units.  ``assigned``: the centroids the
+    last round assigned by, which ``counts`` [K], ``sums`` [K][d] (of offsets
+    x - QueryMin), ``sq_sums`` [K] and ``sse`` (a Fraction, record units) refer
+    to.  ``converged_at``: the first round whose update changed nothing, None
+    when every update moved a centroid.  ``rounds``: the rounds' SurveyResults."""
+    centroids: list
+    points: list
+    assigned: list
+    counts: list
+    sums: list
+    sq_sums: list
+    sse: object
+    converged_at: object = None
+    rounds: list = field(default_factory=list)
 
 
 class DrynxClient:
@@ -380,6 +403,88 @@ class DrynxClient:
             raise RuntimeError(f"iterative quantile {iter_id}: no records in the domain")
         return float(op.QueryMin + prefixes[0]), rounds
 
+    # ------------------------------------------------------------------ k-means
+    def kmeans_round_query(self, sq: SurveyQuery, r: int, centroids, search_id: str) -> SurveyQuery:
+        """Round ``r`` of the k-means run ``search_id`` as a survey of its own: a
+        copy of the ``kmeans`` survey ``sq`` whose ``Operation.KMeans`` carries the
+        round and the centroids it assigns by, with the survey's ranges and
+        input-validation signatures (the same objects every round, so the
+        provers' and verifiers' tables built for round 0 serve the others) and
+        a survey id derived from ``search_id``."""
+        op = sq.Query.Operation
+        if op.NameOp != "kmeans" or op.KMeans is None:
+            raise ValueError(f"a k-means run needs a kmeans survey, not {op.NameOp}")
+        rq = copy.copy(sq)
+        rq.Query = copy.copy(sq.Query)
+        rq.Query.Operation = copy.copy(op)
+        p = op.KMeans
+        rq.Query.Operation.KMeans = KMeansParameters(K=p.K, Scale=p.Scale, Round=int(r), Rounds=p.Rounds,
+                                                     Centroids=[int(c) for c in centroids], SearchID=search_id)
+        rq.SurveyID = f"{search_id}.r{r}"  # no '/': ledger buckets and proof keys are '<survey id>/<kind>/...'
+        return rq
+
+    def send_kmeans(self, sq: SurveyQuery, centroids, on_round=None, stop_when_converged=False) -> KMeansResult:
+        """K-means clustering (extension) of the records the ``kmeans`` survey
+        ``sq`` reads (``make_kmeans_survey``), from the K * d scaled start
+        ``centroids``: ``KMeans.Rounds`` Lloyd rounds, every one an ordinary
+        verifiable query (its own survey id, proofs and block) whose K * (d +
+        2) outputs are the per-cluster counts, coordinate sums and sums of
+        squares under the centroids the round carries in clear; the querier
+        moves the centroids with ``kmeans.update`` (exact, half up; an empty
+        cluster stays).  ``on_round(r, answer, result)`` is called after each
+        round with the decrypted aggregate.  Exactly ``Rounds`` rounds run,
+        unless ``stop_when_converged`` ends the run after the first round whose
+        update changed nothing -- with a single rank only: the other ranks of a
+        ``comm`` serve a fixed count (``serve_kmeans``).  Replicated groups
+        (``GroupByValues``) must agree.  Returns a ``KMeansResult``."""
+        op = sq.Query.Operation
+        if op.NameOp != "kmeans" or op.KMeans is None:
+            raise ValueError(f"a k-means run needs a kmeans survey, not {op.NameOp}")
+        p, d = op.KMeans, op.NbrInput
+        cur = [int(c) for c in centroids]
+        km.check(p.K, d, op.QueryMin, op.QueryMax, p.Scale, cur)
+        km.check_rounds(p.Rounds)
+        collective = getattr(getattr(self.entry, "comm", None), "world", 1) > 1
+        if stop_when_converged and collective:
+            raise ValueError("stop_when_converged with several ranks: the other ranks serve exactly Rounds rounds")
+        search_id = sq.SurveyID or new_survey_id()
+
+        def answers(partial):
+            """Per group the round's aggregate, decrypted as integers."""
+            with timers.timed("Decode"):
+                return [[int(v) for v in eg.decrypt_auto(self.keypair.secret, cv.to(self.device),
+                                                         self.decrypt_bound).cpu().tolist()]
+                        for cv in partial.groups()]
+
+        rounds, failed, converged_at, answer, assigned = [], None, None, None, cur
+        for r in range(p.Rounds):
+            rq = self.kmeans_round_query(sq, r, cur, search_id)
+            if r == 0 and not check_parameters(rq, False):
+                raise ValueError("the k-means query fails CheckParameters")
+            res = self.entry.run_survey(rq, on_result=answers)
+            rounds.append(res)
+            if failed is None:
+                outs = res.client_out
+                if not outs or any(x != outs[0] for x in outs):
+                    failed = f"round {r}: the groups disagree on the clusters' sums"
+                else:
+                    answer, assigned = outs[0], cur
+                    cur = km.update(assigned, answer, p.K, d, p.Scale)
+                    if cur == assigned and converged_at is None:
+                        converged_at = r
+                    if on_round is not None:
+                        on_round(r, answer, res)
+            # With several ranks the others serve exactly Rounds rounds: a failed run still runs them all.
+            if failed is not None and not collective:
+                break
+            if stop_when_converged and converged_at is not None:
+                break
+        if failed is not None:
+            raise RuntimeError(f"k-means {search_id}: {failed}")
+        counts, sums, sq_sums = km.split(answer, p.K, d)
+        return KMeansResult(cur, km.points(cur, p.K, d, op.QueryMin, p.Scale), assigned, counts, sums, sq_sums,
+                            km.sse(answer, p.K, d), converged_at, rounds)
+
     # ------------------------------------------------------------------ VN / skipchain calls
     def send_survey_query_to_vns(self, sq: SurveyQuery):
         """SendSurveyQueryToVNs (api_skipchain.go:16): announce the survey to the
@@ -423,6 +528,17 @@ def serve_iterative(node) -> list:
     op = sq.Query.Operation
     L = iter_rounds(op.QueryMin, op.QueryMax, sq.IterBase)
     return [res] + [node.run_survey(None) for _ in range(L - 1)]
+
+
+def serve_kmeans(node) -> list:
+    """A rank without the querier serves one k-means run: one
+    ``run_survey(None)`` per round, the number of rounds read from the first
+    round's query.  Returns the rounds' SurveyResults."""
+    res = node.run_survey(None)
+    op = node.surveys[res.survey_id].Query.Operation
+    if op.NameOp != "kmeans" or op.KMeans is None:
+        raise RuntimeError(f"survey {res.survey_id} is not a round of a k-means query")
+    return [res] + [node.run_survey(None) for _ in range(op.KMeans.Rounds - 1)]
 
 
 def lr_parameters(**kw) -> LogisticRegressionParameters:

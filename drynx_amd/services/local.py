@@ -114,6 +114,33 @@ def make_iterative_survey(client: DrynxClient, cluster, op_name: str, base: int,
     return sq
 
 
+def make_kmeans_survey(client: DrynxClient, cluster, k: int, d: int, scale: int, rounds: int, *, query_min=0,
+                       query_max=10, rows=10, group_by=(1,), proofs=0, ranges=None, thresholds=None, survey_id=None,
+                       sig_device="cpu", deterministic_sigs=False, verification_sharding=0, with_vns=None,
+                       range_proof_mode=0):
+    """The survey ``DrynxClient.send_kmeans(sq, centroids)`` runs in rounds:
+    ``k`` clusters of records with ``d`` columns over [query_min, query_max],
+    centroids in units of 1 / ``scale``, ``rounds`` Lloyd rounds.  Its k * (d +
+    2) outputs are counts and sums: with proofs the ``ranges`` given ((u, l),
+    or one per output) must hold a DP's largest sum of squares, and they and
+    the input-validation signatures are made once and shared by every round."""
+    from ..query import KMeansParameters, kmeans_operation
+
+    op = kmeans_operation(query_min, query_max, d, k)
+    if proofs and ranges is None:
+        raise ValueError("a k-means survey with proofs needs the ranges of its sums")
+    # (a survey with as many outputs: make_survey sizes the ranges and signatures by them)
+    sq = make_survey(client, cluster, "frequencyCount", query_min=query_min, query_max=query_min + op.NbrOutput - 1,
+                     rows=rows, group_by=group_by, proofs=proofs, ranges=ranges if proofs else None,
+                     thresholds=thresholds, survey_id=survey_id, sig_device=sig_device,
+                     deterministic_sigs=deterministic_sigs, verification_sharding=verification_sharding,
+                     with_vns=with_vns, range_proof_mode=range_proof_mode)
+    op.KMeans = KMeansParameters(K=int(k), Scale=int(scale), Round=0, Rounds=int(rounds))
+    sq.Query.Operation = op
+    sq.Query.DPDataGen.GenerateDataMax = int(query_max)
+    return sq
+
+
 def clear_expected(op_name, clear_dp: dict):
     """Sum of the DPs' clear responses (first group) for checking decoded results."""
     tot = None
@@ -123,5 +150,5 @@ def clear_expected(op_name, clear_dp: dict):
     return tot
 
 
-__all__ = ["local_cluster", "make_survey", "make_iterative_survey", "make_signatures", "RANGE_PRESETS",
-           "clear_expected", "O"]
+__all__ = ["local_cluster", "make_survey", "make_iterative_survey", "make_kmeans_survey", "make_signatures",
+           "RANGE_PRESETS", "clear_expected", "O"]

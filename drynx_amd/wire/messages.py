@@ -17,7 +17,8 @@ import uuid
 
 from ..crypto import oracle as O
 from ..query import (LogisticRegressionParameters, Operation, PublishSignatureBytes, Query, QueryDiffP,
-                     QueryDPDataGen, QueryIVSigs, Roster, ServerIdentity, SurveyQuery, sql_from_dict)
+                     QueryDPDataGen, QueryIVSigs, Roster, ServerIdentity, SurveyQuery, kmeans_from_dict,
+                     sql_from_dict)
 from . import onet
 
 
@@ -71,7 +72,9 @@ def survey_query_to_msg(sq: SurveyQuery) -> dict:
         "Query": {
             "Operation": {"NameOp": op.NameOp, "NbrInput": op.NbrInput, "NbrOutput": op.NbrOutput,
                           "QueryMin": op.QueryMin, "QueryMax": op.QueryMax,
-                          "LRParameters": {k: v for k, v in lr.__dict__.items() if k != "NbrTargets"}},
+                          "LRParameters": {k: v for k, v in lr.__dict__.items() if k != "NbrTargets"},
+                          "KMeans": None if op.KMeans is None else
+                          dict(op.KMeans.__dict__, Centroids=[int(c) for c in op.KMeans.Centroids])},
             "Ranges": [list(r) for r in (q.Ranges or [])],
             "Proofs": q.Proofs,
             "Obfuscation": q.Obfuscation,
@@ -121,7 +124,8 @@ def survey_query_from_msg(d: dict) -> SurveyQuery:
         ServerToDP={k: [server_identity_from_msg(s) for s in v] for k, v in d["ServerToDP"].items()},
         Query=Query(
             Operation=Operation(op.get("NameOp", ""), op.get("NbrInput", 0), op.get("NbrOutput", 0),
-                                op.get("QueryMin", 0), op.get("QueryMax", 0), lrp),
+                                op.get("QueryMin", 0), op.get("QueryMax", 0), lrp,
+                                kmeans_from_dict(op.get("KMeans"))),  # absent (every other operation): None
             Ranges=[list(r) for r in q.get("Ranges", [])] or None,
             Proofs=q.get("Proofs", 0),
             Obfuscation=q.get("Obfuscation", False),

@@ -43,8 +43,14 @@ LR_PARAMETERS = (("DatasetName", "string"), ("FilePath", "string"), ("NbrRecords
                  ("K", "sint"), ("PrecisionApproxCoefficients", "double"),
                  # drynx_amd extension (after the reference fields): 1 = distinct-coefficient packing of level 2
                  ("Packing", "sint"))
+# drynx_amd extension: one round of a k-means query (query.KMeansParameters)
+KMEANS_PARAMETERS = (("K", "sint"), ("Scale", "sint"), ("Round", "sint"), ("Rounds", "sint"),
+                     ("Centroids", ("rep", "sint")), ("SearchID", "string"))
 OPERATION = (("NameOp", "string"), ("NbrInput", "sint"), ("NbrOutput", "sint"), ("QueryMin", "sint"),
-             ("QueryMax", "sint"), ("LRParameters", ("msg", LR_PARAMETERS)))
+             ("QueryMax", "sint"), ("LRParameters", ("msg", LR_PARAMETERS)),
+             # drynx_amd extension (after the reference fields): sent for the operation "kmeans" only; None for
+             # every other operation is not encoded, so their surveys keep their bytes
+             ("KMeans", ("msg", KMEANS_PARAMETERS)))
 QUERY_DIFFP = (("LapMean", "double"), ("LapScale", "double"), ("NoiseListSize", "sint"), ("Quanta", "double"),
                ("Scale", "double"), ("Limit", "double"))
 QUERY_DPDATAGEN = (("GroupByValues", ("rep", "sint")), ("GenerateRows", "sint"), ("GenerateDataMin", "sint"),
